@@ -15,6 +15,14 @@ Multi-GPU: strong scaling of the same frame — the V x tile-row render stripes 
 of dL/dmeans3D per frame; the simulation replicated, or (--shard-sim, default from 100k particles per rank)
 particle-sharded with two block all-reduces per substep (neuma_amd/harness.py, neuma_amd/sim/shard.py).
 Prints ONE JSON line on rank 0.
+
+A plain run does what the headline needs and nothing more: set up, warm up, time the K frames, print the line
+(`value` frames/s, `ms_per_step`).  `--full` adds everything else the line has carried: the profiled frame and the sampled
+dominant-kernel events behind `roofline` / `kernel_rooflines` / `kernel_breakdown_ms_per_frame`, view statistics, component
+rates, the per-rank report of N > 1, the BPTT epoch / training measurements (`--epoch-frames`) and the CPU baseline
+(unless `--no-cpu-baseline`).  `--dump-outputs DIR` writes what the last timed frame handed its caller (loss, particle
+positions and deformation gradients, LoRA gradients) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared
+array by array.
 """
 import argparse
 import json
@@ -37,6 +45,36 @@ def prof_table(lib):
         name = name.strip("()")          # (template instances with a comma are launched through a parenthesised macro argument)
         out[name] = (int(calls), float(ms))
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, rt, last, loss_total):
+    """--dump-outputs: the arrays the timed path returned to its caller in the last timed frame - the frame's loss (summed over
+    the ranks), the particle positions x (N, 3) and deformation gradients F (N, 3, 3) of FrameResult, and the gradients the
+    frame accumulated into the trainable parameters (.grad) - as <name>.npy, float32 (the loss float64).  Over 64 MB in all,
+    the per-particle arrays keep a fixed, seeded sample of rows (sample_rows.npy holds their indices)."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {"loss": np.array([loss_total], dtype=np.float64),
+              "x": last.x.detach().float().cpu().numpy(),
+              "F": last.F.detach().float().cpu().numpy()}
+    for net_name, net in (("elasticity", rt.elasticity), ("plasticity", rt.plasticity)):
+        for name, prm in net.named_parameters():
+            if prm.requires_grad and prm.grad is not None:
+                arrays[f"grad.{net_name}.{name}"] = prm.grad.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = arrays["x"].shape[0]
+        per_row = (arrays["x"].nbytes + arrays["F"].nbytes) / n
+        keep = max(1, int((DUMP_LIMIT_BYTES - (total - per_row * n)) // (per_row + 8)))
+        rows = np.sort(np.random.default_rng(0).choice(n, size=min(n, keep), replace=False))
+        arrays["x"], arrays["F"] = arrays["x"][rows], arrays["F"][rows]
+        arrays["sample_rows"] = rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a))
 
 
 # algorithmic flop per particle and launch of the constitutive kernels (see the roofline block in main)
@@ -262,7 +300,12 @@ def main():
     ap.add_argument("--state", choices=("rest", "deformed", "impact"), default="rest",
                     help="state each timed frame starts from: rest (SURVEY §8d generator), deformed (F = I + 0.05 N(0,1)), "
                          "impact (post-floor-contact checkpoint) - see SceneRuntime.set_start_state")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: profiled frame, roofline and per-kernel figures, view "
+                         "statistics, component rates, per-rank report (N > 1), epoch / training measurements, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed frame returned (loss, x, F, parameter gradients) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--per-op", action="store_true", help="use the per-operator drop-in path instead of the fused roll-out")
     ap.add_argument("--shard-sim", choices=("auto", "on", "off"), default="auto",
                     help="N > 1: particle-sharded simulation (neuma_amd/sim/shard.py) instead of a replicated one; "
@@ -273,8 +316,11 @@ def main():
                     help="also measure a native multi-frame BPTT epoch (SceneRuntime.epoch; finetune.py:331-414 - the reference's "
                          "real unit of work) of this many frames at the workload's S and V, and a 400 x 1 x 1 epoch at bb size, "
                          "as a SECONDARY object `epoch` of the result line (one GPU only; 0 = skip).  19 x 20 x 3 = "
-                         "configs/realworld/finetune-burger.yaml:107-113, 400 x 1 x 1 = configs/synthetic/finetune-bb.yaml:103-107")
+                         "configs/realworld/finetune-burger.yaml:107-113, 400 x 1 x 1 = configs/synthetic/finetune-bb.yaml:103-107; "
+                         "--full only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU, rendezvous on 127.0.0.1)
@@ -367,10 +413,12 @@ def main():
     if args.state != "rest":
         rt.set_start_state(args.state)
     rt.make_ground_truth()
-    # touched grid nodes of the initial state (roofline accounting) and (Gaussian, tile) pairs per view
-    with torch.no_grad():
-        rt.rollout(*(t[rt.rows] for t in rt.start))
-        _, rt.touched_nodes = rt.model.grid_stats()
+    rt.touched_nodes = None
+    if args.full:
+        # touched grid nodes of the initial state (roofline accounting) and (Gaussian, tile) pairs per view
+        with torch.no_grad():
+            rt.rollout(*(t[rt.rows] for t in rt.start))
+            _, rt.touched_nodes = rt.model.grid_stats()
 
     def sync():
         torch.cuda.synchronize(dev)
@@ -387,55 +435,63 @@ def main():
         for p in params:
             p.grad = None
 
-    # ---- pick the dominant kernel from a fully profiled frame (outside the timed region)
     for _ in range(max(1, args.warmup)):
         zero_grads()
         rt.frame()
     sync()
-    lib.nm_prof_reset()
-    lib.nm_prof_enable(1, None)
-    zero_grads()
-    # per-kernel durations are taken with the views rendered one after another: on concurrent streams the compositing
-    # kernels of different views stretch each other (450 -> 690 us) and the comparison between kernels would be skewed
-    overlap, rt.overlap_views = rt.overlap_views, False
-    rt.frame()
-    sync()
-    rt.overlap_views = overlap
-    lib.nm_prof_enable(0, None)
-    full = prof_table(lib)
-    lib.nm_prof_reset()
-    by_base = {}
-    for name, (calls, ms) in full.items():      # template instances (k_material_bwd<...>) count as one kernel
-        b = name.split("<")[0]
-        by_base[b] = (by_base.get(b, (0, 0.0))[0] + calls, by_base.get(b, (0, 0.0))[1] + ms)
-    dom_base = max(by_base.items(), key=lambda kv: kv[1][1])[0] if by_base else "k_render_bwd"
+    full, dom_base, prof_stride = {}, None, 1
+    if args.full:
+        # ---- pick the dominant kernel from a fully profiled frame (outside the timed region)
+        lib.nm_prof_reset()
+        lib.nm_prof_enable(1, None)
+        zero_grads()
+        # per-kernel durations are taken with the views rendered one after another: on concurrent streams the compositing
+        # kernels of different views stretch each other (450 -> 690 us) and the comparison between kernels would be skewed
+        overlap, rt.overlap_views = rt.overlap_views, False
+        rt.frame()
+        sync()
+        rt.overlap_views = overlap
+        lib.nm_prof_enable(0, None)
+        full = prof_table(lib)
+        lib.nm_prof_reset()
+        by_base = {}
+        for name, (calls, ms) in full.items():      # template instances (k_material_bwd<...>) count as one kernel
+            b = name.split("<")[0]
+            by_base[b] = (by_base.get(b, (0, 0.0))[0] + calls, by_base.get(b, (0, 0.0))[1] + ms)
+        dom_base = max(by_base.items(), key=lambda kv: kv[1][1])[0] if by_base else "k_render_bwd"
 
-    # ---- timed region: K frames, HIP events on the dominant kernel only
-    # (a pair of event records costs ~11 us of bubble around the launch - 19 x that per metric frame would be 3 % of the very
-    #  rate being measured - so a kernel launched many times per frame is timed at every 8th launch: still hundreds of live
-    #  samples over the timed region, spread over all substeps)
-    dom_per_frame = by_base.get(dom_base, (1, 0.0))[0]
-    prof_stride = 8 if dom_per_frame >= 8 else 1
-    lib.nm_prof_enable(prof_stride, dom_base.encode())
-    sync()
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+        # HIP events on the dominant kernel only inside the timed region
+        # (a pair of event records costs ~11 us of bubble around the launch - 19 x that per metric frame would be 3 % of the very
+        #  rate being measured - so a kernel launched many times per frame is timed at every 8th launch: still hundreds of live
+        #  samples over the timed region, spread over all substeps)
+        dom_per_frame = by_base.get(dom_base, (1, 0.0))[0]
+        prof_stride = 8 if dom_per_frame >= 8 else 1
+        lib.nm_prof_enable(prof_stride, dom_base.encode())
+        sync()
+
+    # ---- timed region: K frames (with --full: per-frame GPU timeline events as well)
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if args.full else None
     import gc
     gc.collect()
     gc.disable()            # no collector pauses inside the timed region (a gen-2 pass costs milliseconds with this many tensors alive)
     t0 = time.perf_counter()
     last = None
-    marks[0].record()
+    if marks:
+        marks[0].record()
     for it in range(args.steps):
         zero_grads()
         last = rt.frame()
-        marks[it + 1].record()          # per-frame GPU timeline (no host sync inside the timed region)
+        if marks:
+            marks[it + 1].record()          # per-frame GPU timeline (no host sync inside the timed region)
     sync()
     elapsed = time.perf_counter() - t0
     gc.enable()
     rt.flush()              # anything a frame reported late (exchange status, rasterizer overflow) surfaces here, loudly
-    per_frame = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
-    lib.nm_prof_enable(0, None)
-    dom = prof_table(lib)
+    per_frame = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)) if marks else None
+    dom = {}
+    if args.full:
+        lib.nm_prof_enable(0, None)
+        dom = prof_table(lib)
     elapsed_local = elapsed
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
@@ -450,37 +506,41 @@ def main():
         t = torch.tensor([loss_local], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         loss_total = float(t)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rt, last, loss_total)
 
     # (Gaussian, tile) pairs, list entries and walked list entries of one full view, for the byte accounting
     D, vstats = 0.0, None
-    try:
-        from neuma_amd.tune import compute_bindings_xyz, compute_bindings_F
-        with torch.no_grad():
-            m3 = compute_bindings_xyz(last.x, rt.start[0], rt.g_start, rt.bindings)
-            dg = compute_bindings_F(last.F, rt.bindings)
-            from neuma_amd.render import deform_cov_by_F, get_rasterizer, view_stats
-            cov = deform_cov_by_F(rt._cov, dg)
-            rast = get_rasterizer(rt.cameras[0], rt.gaussians.active_sh_degree, False, rt.background)
-            vstats = view_stats(rast, m3.contiguous(), rt._opacity, shs=rt._shs, cov3D_precomp=cov)
-            D = float(vstats["pairs"])
-    except Exception as e:  # accounting only
-        print(f"[bench] view statistics unavailable: {e}", file=sys.stderr)
+    if args.full:
+        try:
+            from neuma_amd.tune import compute_bindings_xyz, compute_bindings_F
+            with torch.no_grad():
+                m3 = compute_bindings_xyz(last.x, rt.start[0], rt.g_start, rt.bindings)
+                dg = compute_bindings_F(last.F, rt.bindings)
+                from neuma_amd.render import deform_cov_by_F, get_rasterizer, view_stats
+                cov = deform_cov_by_F(rt._cov, dg)
+                rast = get_rasterizer(rt.cameras[0], rt.gaussians.active_sh_degree, False, rt.background)
+                vstats = view_stats(rast, m3.contiguous(), rt._opacity, shs=rt._shs, cov3D_precomp=cov)
+                D = float(vstats["pairs"])
+        except Exception as e:  # accounting only
+            print(f"[bench] view statistics unavailable: {e}", file=sys.stderr)
     Dacc = vstats if (vstats is not None and world == 1) else D
 
     pmc, pmc_mfma, pmc_stale, pmc_digest = {}, {}, None, None
-    try:        # HBM bytes per launch and matrix-pipe counters from the committed PMC passes (profiles/pmc_traffic.json, tools/make_profile_md.py)
-        _p = json.loads((ROOT / "profiles" / "pmc_traffic.json").read_text())
-        pmc_digest = _p.get("csrc_digest")
-        # the counters are copies: valid only for the sources they were measured on.  A library built from other sources gets
-        # no traffic figure at all (roofline.traffic null, no *_static fields) and the line says so
-        pmc_stale = pmc_digest != _lib.csrc_digest()
-        if not pmc_stale:
-            pmc, pmc_mfma = _p.get("kernels", {}), _p.get("mfma", {})
-        else:
-            print(f"[bench] profiles/pmc_traffic.json was measured on sources {pmc_digest}, this checkout is {_lib.csrc_digest()}: "
-                  "counter-derived fields dropped (pmc_stale)", file=sys.stderr)
-    except Exception:
-        pass
+    if args.full:
+        try:        # HBM bytes per launch and matrix-pipe counters from the committed PMC passes (profiles/pmc_traffic.json, tools/make_profile_md.py)
+            _p = json.loads((ROOT / "profiles" / "pmc_traffic.json").read_text())
+            pmc_digest = _p.get("csrc_digest")
+            # the counters are copies: valid only for the sources they were measured on.  A library built from other sources gets
+            # no traffic figure at all (roofline.traffic null, no *_static fields) and the line says so
+            pmc_stale = pmc_digest != _lib.csrc_digest()
+            if not pmc_stale:
+                pmc, pmc_mfma = _p.get("kernels", {}), _p.get("mfma", {})
+            else:
+                print(f"[bench] profiles/pmc_traffic.json was measured on sources {pmc_digest}, this checkout is {_lib.csrc_digest()}: "
+                      "counter-derived fields dropped (pmc_stale)", file=sys.stderr)
+        except Exception:
+            pass
     roof = None
     if dom:
         calls = sum(v[0] for v in dom.values())
@@ -524,7 +584,7 @@ def main():
 
     # ---- component rates, measured outside the timed region with HIP events on torch's stream
     rates = None
-    if rank == 0 or world > 1:
+    if args.full and (rank == 0 or world > 1):
         from neuma_amd.tune import compute_bindings_xyz, compute_bindings_F
 
         def gpu_ms(fn, reps=3):
@@ -569,7 +629,7 @@ def main():
 
     # ---- N > 1: what every rank spent where, so that a scaling run explains itself (one line per rank on stderr + `per_rank`)
     per_rank = None
-    if world > 1:
+    if args.full and world > 1:
         from neuma_amd.sim.shard import all_reduce_sum_, gather_rows
 
         def coll_us(fn, reps=20):
@@ -608,7 +668,7 @@ def main():
                       f"rates {g['rates']}, collectives {g['collectives']}", file=sys.stderr)
 
     epoch = None
-    if rank == 0 and world == 1 and args.epoch_frames > 0 and not args.per_op:
+    if args.full and rank == 0 and world == 1 and args.epoch_frames > 0 and not args.per_op:
         try:
             epoch = {"unit": "frames/s inside one epoch = F frames forward (state flowing from frame to frame, renders of frame f under "
                              "the simulation of frame f+1) + one reverse sweep; finetune.py:331-414",
@@ -645,7 +705,7 @@ def main():
             epoch = {"error": f"{type(e).__name__}: {e}"}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:      # reported at N=1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:      # reported at N=1 only
         try:
             from oracle import cpu_baseline as cbaseline
             cpu = cbaseline.time_frame_sample(scene, rt)
@@ -673,45 +733,49 @@ def main():
         devices = gathered
     if rank == 0:
         cfg = scene.cfg
-        total_ms = sum(v[1] for v in full.values()) or 1.0
         out = {
             "metric": "sim+render frames/sec (fwd+bwd), 100k pts / 128^3 grid / 1080p",
             "value": round(fps, 4), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": bool(args.full),
             "config": {"workload": f"{args.workload}: {cfg['N']} particles / {cfg['G']}^3 grid / {cfg['K']} Gaussians / "
                                    f"{cfg['W']}x{cfg['H']}", "substeps_per_frame": cfg["S"], "views_per_frame": cfg["V"],
                        "sh_degree": cfg["sh"], "material": cfg["mat"] + "_0300 + LoRA r16", "path": "per-op" if args.per_op else ("fused-rollout (library-level sharded loop)" if shard_sim else "fused-rollout"),
                        "parallelism": (("particle-sharded sim" if shard_sim else "replicated sim") + " + render stripes") if world > 1 else "single GPU",
-                       "start_state": rt.state_kind,
-                       "touched_grid_nodes": int(rt.touched_nodes), "gaussian_tile_pairs_per_view": int(D)},
+                       "start_state": rt.state_kind},
             "world": world, "backend": ({"nccl": "rccl"}.get(backend, backend) if world > 1 else None),
             "shard_collectives": getattr(getattr(rt.model, "exchange", None), "link_backend", None),
             "rccl_version": ".".join(str(v) for v in torch.cuda.nccl.version()) if hasattr(torch.cuda, "nccl") else None,
             "devices": devices,
-            "roofline": roof,
-            "pmc_stale": pmc_stale, "pmc_csrc_digest": pmc_digest, "csrc_digest": _lib.csrc_digest(),
-            "cpu_baseline": cpu,
-            "epoch": epoch,
-            "kernel_breakdown_ms_per_frame": {k: round(v[1], 3) for k, v in sorted(full.items(), key=lambda kv: -kv[1][1])[:12]},
-            "kernel_time_fraction_of_frame": round(total_ms / (1e3 * elapsed / args.steps), 3),
-            "kernel_time_note": "sum of the HIP-event durations of every launch of ONE profiled frame (its views rendered one after "
-                                "the other so that the events do not overlap) over the timed frame time; the timed frames run their V "
-                                "views on V streams side by side, so the sum exceeds the frame (> 1)",
+            "csrc_digest": _lib.csrc_digest(),
             "timed_region_s": round(elapsed, 4),
-            "view_stats": vstats,
             "shard_cost_model": cost if world > 1 else None,
-            "per_rank": per_rank,
-            "kernel_rooflines": kernel_rooflines(full, rt, Dacc, *((pmc, pmc_mfma) if (args.workload == "metric" and world == 1) else (None, None))),
-            "kernel_rooflines_static_note": "traffic_static / frac_of_executed_flops / mfma_busy_pct: copied from profiles/pmc_traffic.json "
-                                            "(rocprofv3 --pmc passes of this workload and build), not measured by this run",
-            "roofline_frame": frame_roofline(full, rt, Dacc, elapsed / args.steps),
-            "frame_ms_gpu": {"median": round(per_frame[len(per_frame) // 2], 3), "p10": round(per_frame[len(per_frame) // 10], 3),
-                             "p90": round(per_frame[(9 * len(per_frame)) // 10], 3)},
-            "rates": rates,
             "loss": loss_total,
             "loss_rank0_part": loss_local,
         }
+        if args.full:
+            total_ms = sum(v[1] for v in full.values()) or 1.0
+            out["config"].update({"touched_grid_nodes": int(rt.touched_nodes), "gaussian_tile_pairs_per_view": int(D)})
+            out.update({
+                "roofline": roof,
+                "pmc_stale": pmc_stale, "pmc_csrc_digest": pmc_digest,
+                "cpu_baseline": cpu,
+                "epoch": epoch,
+                "kernel_breakdown_ms_per_frame": {k: round(v[1], 3) for k, v in sorted(full.items(), key=lambda kv: -kv[1][1])[:12]},
+                "kernel_time_fraction_of_frame": round(total_ms / (1e3 * elapsed / args.steps), 3),
+                "kernel_time_note": "sum of the HIP-event durations of every launch of ONE profiled frame (its views rendered one after "
+                                    "the other so that the events do not overlap) over the timed frame time; the timed frames run their V "
+                                    "views on V streams side by side, so the sum exceeds the frame (> 1)",
+                "view_stats": vstats,
+                "per_rank": per_rank,
+                "kernel_rooflines": kernel_rooflines(full, rt, Dacc, *((pmc, pmc_mfma) if (args.workload == "metric" and world == 1) else (None, None))),
+                "kernel_rooflines_static_note": "traffic_static / frac_of_executed_flops / mfma_busy_pct: copied from profiles/pmc_traffic.json "
+                                                "(rocprofv3 --pmc passes of this workload and build), not measured by this run",
+                "roofline_frame": frame_roofline(full, rt, Dacc, elapsed / args.steps),
+                "frame_ms_gpu": {"median": round(per_frame[len(per_frame) // 2], 3), "p10": round(per_frame[len(per_frame) // 10], 3),
+                                 "p90": round(per_frame[(9 * len(per_frame)) // 10], 3)},
+                "rates": rates,
+            })
     else:
         out = None
     if dist.is_initialized():

@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 
 
-def _bench(gpus, workload="tiny", shard="auto", exchange=None, steps=3, warmup=1, timeout=600):
+def _bench(gpus, workload="tiny", shard="auto", exchange=None, steps=3, warmup=1, timeout=600, full=True, extra=()):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("NEUMA_SHARD_EXCHANGE", None)
     if gpus > 1:
@@ -25,7 +25,7 @@ def _bench(gpus, workload="tiny", shard="auto", exchange=None, steps=3, warmup=1
     if exchange:
         env["NEUMA_SHARD_EXCHANGE"] = exchange
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", str(gpus), "--steps", str(steps), "--warmup", str(warmup), "--workload", workload,
-           "--no-cpu-baseline", "--epoch-frames", "0", "--shard-sim", shard]
+           "--no-cpu-baseline", "--epoch-frames", "0", "--shard-sim", shard] + (["--full"] if full else []) + list(extra)
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert p.returncode == 0, f"rc {p.returncode}\n{p.stderr[-3000:]}"
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -86,3 +86,23 @@ def test_bench_two_ranks_auto_decision_bb():
     assert m is not None and "shard" in m
     assert len({r["shard_sim"] for r in d["per_rank"]}) == 1
     assert ("particle-sharded" in d["config"]["parallelism"]) == bool(d["per_rank"][0]["shard_sim"])
+
+
+def test_bench_plain_line_and_dumped_outputs(one_rank, tmp_path):
+    """A plain run (no --full) times exactly --steps frames and prints the headline fields only; --dump-outputs writes what the
+    last timed frame returned (loss, x, F, the LoRA gradients) as float .npy files, and its loss is the --full run's."""
+    import numpy as np
+    d = _bench(1, steps=4, full=False, extra=("--dump-outputs", str(tmp_path)))
+    assert d["steps"] == 4 and d["full"] is False and d["ms_per_step"] > 0 and d["value"] > 0
+    assert abs(d["ms_per_step"] - 1e3 / d["value"]) <= 1e-3 * d["ms_per_step"] + 1e-3
+    assert d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert "roofline" not in d and "epoch" not in d and "cpu_baseline" not in d
+    files = {f.stem: np.load(f) for f in tmp_path.glob("*.npy")}
+    assert {"loss", "x", "F"} <= set(files) and sum(f.nbytes for f in files.values()) <= 64 << 20
+    assert files["x"].shape == (2000, 3) and files["F"].shape == (2000, 3, 3)
+    grads = [k for k in files if k.startswith("grad.")]
+    assert len(grads) == 12 and all(files[k].dtype == np.float32 and np.isfinite(files[k]).all() for k in grads)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    ref = one_rank["tiny"]["loss"]
+    assert float(files["loss"][0]) == d["loss"]
+    assert measured(abs(d["loss"] - ref) / abs(ref), "loss, plain run vs --full run (rel)") < 1e-5

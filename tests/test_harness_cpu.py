@@ -301,11 +301,10 @@ def test_cache_pool_accounting_per_device_trim_and_retry(monkeypatch):
         R.lease_cache(5000, "cpu", force=True)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/experiments/configs/demo"), reason="needs the reference checkout (build container only)")
-def test_inference_entry_point_reads_the_reference_demo_configs():
+def test_inference_entry_point_reads_the_reference_demo_configs(golden_dir):
     """`python -m neuma_amd.inference`: its argument parser mirrors experiments/inference.py:48-84 and the loader turns the four
-    shipped demo YAMLs into what `inference()` consumes (objects, per-object checkpoints / adaptors / velocities, sim block)."""
-    from pathlib import Path
+    shipped demo YAMLs into what `inference()` consumes (objects, per-object checkpoints / adaptors / velocities, sim block).
+    The YAMLs are the reference's experiments/configs/demo/*.yaml, stored unchanged under tests/golden/demo_configs/."""
     from neuma_amd.config import load_config
     from neuma_amd.inference import parse_args
     a = parse_args(["-c", "x.yaml", "-vn", "clip", "-s", "50", "-dv", "e_2", "e_3", "-sp", "run", "-f", "5", "-ri"])
@@ -314,7 +313,7 @@ def test_inference_entry_point_reads_the_reference_demo_configs():
     d = parse_args(["-c", "x.yaml", "-vn", "clip"])
     assert d.eval_steps == 600 and d.debug_views == [] and d.save_particles is None and d.dataset_path is None      # inference.py:54-81
     seen = 0
-    for f in sorted(Path("/root/reference/experiments/configs/demo").glob("*.yaml")):
+    for f in sorted((golden_dir / "demo_configs").glob("*.yaml")):
         c = load_config(f)
         assert len(c.objects) >= 1 and c.sim.num_grids > 0 and c.sim.bc in ("noslip", "freeslip")
         for o in c.objects:
