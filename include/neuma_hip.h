@@ -513,6 +513,34 @@ int nm_raster_backward(const nm_raster_cfg* cfg, int32_t k, int32_t m, const flo
 int nm_pixel_loss(int32_t kind, float weight, int32_t h, int32_t w, int32_t row0, int32_t row1,
                   const float* img, const float* gt, float* loss_out, float* dL_dimg, void* stream);
 
+/* ------------------------------------------------------------------ Gaussian registration (experiments/regist.py) */
+
+/* Register.forward (modules/tune/regist/register.py) + the covariance build (general_utils.py:93-139) for K Gaussians,
+ * one pass.  params (DEVICE, 20 floats): R[9] (row-major), q_R[4] (wxyz), s, t[3], o[3]; xyz (K,3), log_scales (K,3),
+ * rot (K,4) as loaded (normalised here, F.normalize).  Writes
+ *   means3D = R (s (xyz - o)) + t,   log_scales' = log_scales + log s,
+ *   rot'    = normalize(quaternion_multiply(normalize(rot), q_R))          (transform_utils.py:14-23, 218),
+ *   cov6    = strip_symmetric(L L^T), L = build_rotation(rot') diag(scale_modifier exp(log_scales')).
+ * out_log_scales / out_rot may be NULL. */
+int nm_regist_apply(int32_t k, const float* xyz, const float* log_scales, const float* rot, const float* params,
+                    float scale_modifier, float* means3D, float* cov6, float* out_log_scales, float* out_rot, void* stream);
+
+/* Adjoint of nm_regist_apply, reduced over the K Gaussians: dL_dparams (DEVICE, 17 floats: dR[9], dq_R[4], ds, dt[3])
+ * += sum_i of the per-Gaussian chain (R and q_R are independent inputs).  Two-stage, fixed-order reduction with fp64
+ * partials: bitwise reproducible.  workspace: nm_regist_bwd_workspace(k) bytes of device scratch. */
+size_t nm_regist_bwd_workspace(int32_t k);
+int nm_regist_backward(int32_t k, const float* xyz, const float* log_scales, const float* rot, const float* params,
+                       float scale_modifier, const float* dL_dmeans3D, const float* dL_dcov6, float* dL_dparams,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* SSIM loss (modules/d3gs/utils/loss_utils.py:26-66, window 11, sigma 1.5, zero padding, size_average) of two (3,H,W) fp32
+ * images: *loss_out (device float) += weight * (1 - ssim(img, gt)); dL_dimg (may be NULL) += weight * d(1 - ssim)/dimg.
+ * Adds to both, so it composes with nm_pixel_loss called first.  The loss value is deterministic (fixed-order fp64
+ * reduction).  workspace: nm_ssim_workspace(h, w) bytes of device scratch. */
+size_t nm_ssim_workspace(int32_t h, int32_t w);
+int nm_ssim_loss(float weight, int32_t h, int32_t w, const float* img, const float* gt, float* loss_out, float* dL_dimg,
+                 void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 """Tuning glue between simulator and renderer.
 Mirrors /root/reference/modules/tune/utils.py: diff_rasterization 323-421, compute_bindings_xyz 424-448,
 compute_bindings_F 451-472, preprocess_for_rasterization 475-523; modules/nclaw/utils.py:110-118
-(denormalize_points_helper_func); modules/d3gs/utils/loss_utils.py:17-24."""
+(denormalize_points_helper_func); modules/d3gs/utils/loss_utils.py:17-66."""
 import ctypes as C
 from typing import List, Optional
 
@@ -146,6 +146,40 @@ def l2_loss(network_output, gt):
     if _fused_loss_ok(network_output, gt):
         return _PixelLoss.apply(network_output, gt, 1, 0, 0)
     return ((network_output - gt) ** 2).mean()
+
+
+class _SSIM(torch.autograd.Function):
+    """ssim(img1, img2) of loss_utils.py:26-66 (window 11, sigma 1.5, mean over the (3,H,W) map) and d ssim / d img1: one
+    nm_ssim_loss call with weight -1 on a loss word holding 1 (1 - (1 - ssim)) and a zeroed gradient buffer."""
+
+    @staticmethod
+    def forward(ctx, img, gt):
+        lib = L.lib()
+        a = img.detach().contiguous().float()
+        b = gt.detach().contiguous().float()
+        h, w = int(a.shape[-2]), int(a.shape[-1])
+        val = torch.ones((), dtype=torch.float32, device=a.device)
+        grad = torch.zeros_like(a) if ctx.needs_input_grad[0] else None
+        ws = torch.empty(int(lib.nm_ssim_workspace(h, w)), dtype=torch.uint8, device=a.device)
+        L.check(lib.nm_ssim_loss(-1.0, h, w, L.ptr(a), L.ptr(b), L.ptr(val), L.ptr(grad), L.ptr(ws), ws.numel(),
+                                 L.stream_ptr(a.device)), "nm_ssim_loss")
+        ctx.grad = grad
+        return val
+
+    @staticmethod
+    def backward(ctx, g):
+        grad, ctx.grad = ctx.grad, None
+        return (grad * g if grad is not None else None), None
+
+
+def ssim(img1, img2, window_size: int = 11, size_average: bool = True):
+    """loss_utils.py:35-66 on (3,H,W) GPU images (the only form the NeuMA drivers pass), differentiable in img1: the HIP
+    kernel pair of nm_ssim_loss.  Other window sizes / per-image averages are not provided (no eager fall-back)."""
+    if window_size != 11 or not size_average:
+        raise NotImplementedError("ssim: only window_size=11 with size_average=True is provided")
+    if not (_fused_loss_ok(img1, img2) and img1.shape[0] == 3):
+        raise L.NeumaHipError("ssim needs two (3,H,W) images on the GPU, the second without gradient")
+    return _SSIM.apply(img1, img2)
 
 
 def diff_rasterization(x: Tensor, deform_grad: Optional[Tensor], gaussians, view_cam, background_color: Tensor,
