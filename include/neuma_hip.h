@@ -541,6 +541,21 @@ size_t nm_ssim_workspace(int32_t h, int32_t w);
 int nm_ssim_loss(float weight, int32_t h, int32_t w, const float* img, const float* gt, float* loss_out, float* dL_dimg,
                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ image-quality metrics (experiments/evaluation.py) */
+
+/* torchmetrics' PeakSignalNoiseRatio and structural_similarity_index_measure (gaussian window 11, sigma 1.5, k1 0.01, k2 0.03,
+ * data_range = max(preds range, target range), variances clamped at 0) of B images of (C,H,W) fp32 each, preds and target
+ * contiguous (B,C,H,W) on the device.  Writes sse_out[b] (DEVICE, fp64) = sum of (preds - target)^2 over image b and, unless
+ * ssim_out is NULL, ssim_out[b] (DEVICE, fp64) = the mean SSIM over image b's C x (H-10) x (W-10) windows lying inside it (what
+ * torchmetrics' reflect pad + crop leaves).  range_per_image != 0: c1, c2 from each image's own range (one call per frame, as
+ * evaluation.py); 0: from the batch-wide range (torchmetrics on a batched call).  H, W >= 11.  Fixed-order fp64 reductions, no
+ * atomics, no host synchronisation: two calls give identical bits.  workspace: nm_image_metrics_workspace(b, c, h, w) bytes of
+ * device scratch. */
+size_t nm_image_metrics_workspace(int32_t b, int32_t c, int32_t h, int32_t w);
+int nm_image_metrics(int32_t b, int32_t c, int32_t h, int32_t w, const float* preds, const float* target,
+                     int32_t range_per_image, double* sse_out, double* ssim_out, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

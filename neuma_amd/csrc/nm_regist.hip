@@ -4,6 +4,7 @@
 //   nm_regist_backward  its adjoint; per-block fp64 partials, then one fixed-order block: bitwise reproducible, no atomics
 //   nm_ssim_loss        modules/d3gs/utils/loss_utils.py:26-66 fused with its adjoint (separable 11-tap passes over LDS tiles)
 #include "nm_common.h"
+#include "nm_ssim.h"
 
 namespace {
 
@@ -234,13 +235,7 @@ __global__ void __launch_bounds__(256) k_regist_reduce(int nb, const double* __r
 
 // ---------------------------------------------------------------- SSIM
 
-constexpr int kTW = 64, kTH = 16, kR = 5, kWin = 2 * kR + 1;   // output tile 16 x 64 per workgroup, 5-pixel halo
-constexpr int kLW = kTW + 2 * kR, kLH = kTH + 2 * kR;           // 74 x 26 loaded
 constexpr float kC1 = 0.01f * 0.01f, kC2 = 0.03f * 0.03f;
-
-struct Window {
-  float w[kWin];
-};
 
 struct SsimDims {
   int h, w, tx, ty, nblk;
@@ -385,18 +380,6 @@ __global__ void __launch_bounds__(256) k_ssim_bwd(SsimDims D, Window W, float we
     const size_t p = ch * plane + (size_t)gy * D.w + gx;
     grad[p] += scale * (v0 + 2.f * img[p] * v1 + gt[p] * v2);
   }
-}
-
-static Window ssim_window() {
-  // loss_utils.py:26-29: exp(-(x - 5)^2 / (2 sigma^2)) / sum, sigma = 1.5 (the reference builds it in fp32 from python floats)
-  double g[kWin], sum = 0.0;
-  for (int k = 0; k < kWin; ++k) {
-    g[k] = (double)(float)exp(-(double)((k - kR) * (k - kR)) / (2.0 * 1.5 * 1.5));
-    sum += g[k];
-  }
-  Window W;
-  for (int k = 0; k < kWin; ++k) W.w[k] = (float)(g[k] / sum);
-  return W;
 }
 
 }  // namespace
