@@ -556,6 +556,28 @@ int nm_image_metrics(int32_t b, int32_t c, int32_t h, int32_t w, const float* pr
                      int32_t range_per_image, double* sse_out, double* ssim_out, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ------------------------------------------------------------------ particle metrics (modules/tune/metrics.py) */
+
+/* Exact 1-nearest-neighbour search, batched over b pairs of clouds: query (b, n_query, 3) and target (b, n_target, 3) fp32,
+ * contiguous, on the device.  For every query point: idx_out[b][i] (DEVICE, int64) = the index of its nearest target and,
+ * unless d2_out is NULL, d2_out[b][i] (DEVICE, fp64) = that squared distance.  Distances are fp64 from the fp32 coordinates;
+ * the winner is the lexicographic minimum of (distance^2, target index), i.e. scipy cKDTree's fp64 choice except on exact
+ * ties.  A query with a NaN / Inf coordinate gets index 0 and distance NaN.  Both clouds are binned per item into a uniform
+ * grid over their own bounding box (found on the device); no atomics on floating-point values, no host synchronisation: two
+ * calls give identical bits.  workspace: nm_nn_workspace(b, n_query, n_target) bytes of device scratch (0 = invalid sizes).
+ * b < 1, an empty cloud or a too small workspace -> -1 before any device work. */
+size_t nm_nn_workspace(int32_t b, int32_t n_query, int32_t n_target);
+int nm_nearest_neighbors(int32_t b, int32_t n_query, int32_t n_target, const float* query, const float* target,
+                         int64_t* idx_out, double* d2_out, void* workspace, size_t workspace_bytes, void* stream);
+/* Both directions of a Chamfer distance (metrics.py chamfer_distance_kdtree) in one call: p1 (b, n1, 3), p2 (b, n2, 3).
+ * cd12_out[b] / cd21_out[b] (DEVICE, fp64) = the mean over p1 (p2) of the squared distance to its nearest point of p2 (p1),
+ * fixed-order sums; NaN for an item where either cloud holds a NaN / Inf coordinate (other items are unaffected).
+ * idx12 (b, n1) / idx21 (b, n2) (DEVICE, int64): the nearest-neighbour indices, or NULL.  workspace:
+ * nm_chamfer_workspace(b, n1, n2) bytes. */
+size_t nm_chamfer_workspace(int32_t b, int32_t n1, int32_t n2);
+int nm_chamfer(int32_t b, int32_t n1, int32_t n2, const float* p1, const float* p2, double* cd12_out, double* cd21_out,
+               int64_t* idx12, int64_t* idx21, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,6 +141,10 @@ SIGNATURES = {
     "nm_ssim_loss": (C.c_int, [_F, _I32, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
     "nm_image_metrics_workspace": (_SZ, [_I32, _I32, _I32, _I32]),
     "nm_image_metrics": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _SZ, _P]),
+    "nm_nn_workspace": (_SZ, [_I32, _I32, _I32]),
+    "nm_nearest_neighbors": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
+    "nm_chamfer_workspace": (_SZ, [_I32, _I32, _I32]),
+    "nm_chamfer": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "nm_lora_merge": (C.c_int, [_I32, _I32, _I32, _F, _P, _P, _P, _P, _P]),
     "nm_lora_merge_bwd": (C.c_int, [_I32, _I32, _I32, _F, _P, _P, _P, _P, _P, _P]),
     "nm_lora_merge_layers": (C.c_int, [_I32, C.POINTER(nm_lora_layer), _P]),

@@ -1,0 +1,450 @@
+// Exact 1-nearest-neighbour search between point clouds, batched over B pairs, and the Chamfer distance of
+// modules/tune/metrics.py (chamfer_distance_kdtree: one scipy cKDTree per batch item on the host) on the device.
+//
+// Each cloud is binned once, per batch item, into a uniform grid over its own bounding box:
+//   k_nn_box      partial min / max of the finite coordinates and a count of non-finite ones, one per workgroup
+//   k_nn_grid     one thread per item: finish of the partials -> origin, cells per axis (within a cell budget that depends on
+//                 the cloud's size only, so the host sizes the workspace without knowing the data), cell edge per axis
+//   k_nn_count    cell key of every point, and its rank inside its cell (integer atomics on the cell counters)
+//   (rocPRIM exclusive scan of the counters: every cell's first position in the sorted array)
+//   k_nn_scatter  the cloud sorted by cell as float4 {x, y, z, index}
+// The search (k_nn_search) takes the queries in the sorted order of their own cloud, so that the lanes of a wave start in
+// neighbouring cells and walk similar shells.  Each query visits growing shells of target cells around its own (clamped)
+// cell and stops once its best squared distance is at most a lower bound on the squared distance to every unvisited cell:
+// the distance to the slab beyond each face of the visited block, inside the targets' box (valid for queries outside it).
+// Distances are fp64 from the fp32 coordinates, the winner is the lexicographic minimum of (distance^2, target index), so the
+// result does not depend on the order of points inside a cell (nor on the atomics' ranks).  The per-item means are fixed-order
+// fp64 sums over the queries in their ORIGINAL order (k_nn_mean_part, k_nn_mean_finish): two calls give identical bits.
+#include "nm_common.h"
+
+#include <rocprim/rocprim.hpp>
+
+namespace {
+
+constexpr int kNnThreads = 256;
+constexpr int kBoxMaxBlocks = 64;      // bbox partials per item
+constexpr int kMeanMaxBlocks = 64;     // mean partials per item
+constexpr int kPointsPerCell = 2;      // cell budget = ceil(P / 2)
+
+struct NnBoxPart {
+  float lo[3], hi[3];
+  int bad;       // non-finite coordinates seen
+  int pad;
+};
+
+struct NnGrid {          // one per (cloud, item), written by k_nn_grid
+  double o[3];           // box minimum (origin of cell 0)
+  double inv_h[3];       // cells per unit length (0 on a one-cell axis)
+  double h[3];           // cell edge
+  double hi[3];          // box maximum
+  double slack[3];       // rounding allowance of the cell assignment (bounds are lowered by it)
+  int n[3];              // cells per axis, n0 * n1 * n2 <= the cell budget
+  int bad;               // the cloud holds a NaN / Inf coordinate in this item
+};
+
+static inline size_t nn_al(size_t x) { return (x + 255) & ~(size_t)255; }
+static inline int nn_box_blocks(int p) {
+  const int g = nm_div_up(p, kNnThreads * 8);
+  return g < 1 ? 1 : (g > kBoxMaxBlocks ? kBoxMaxBlocks : g);
+}
+static inline int nn_mean_blocks(int p) {
+  const int g = nm_div_up(p, kNnThreads * 16);
+  return g < 1 ? 1 : (g > kMeanMaxBlocks ? kMeanMaxBlocks : g);
+}
+static inline int nn_cell_budget(int p) { return (int)(((int64_t)p + kPointsPerCell - 1) / kPointsPerCell); }
+
+// One binned cloud (B items of P points): where its arrays live in the workspace.
+struct NnBin {
+  int b, p, cmax, gbox;
+  NnBoxPart* part;
+  NnGrid* grid;
+  int* cnt;          // B * cmax + 1 counters
+  int* start;        // their exclusive scan: first global sorted position of every cell, start[B * cmax] = B * P
+  int* key;          // B * P
+  int* rank;         // B * P
+  float4* sorted;    // B * P
+  void* scan_tmp;
+  size_t scan_bytes;
+  size_t total;
+};
+
+static NnBin carve_bin(char* base, int b, int p) {
+  NnBin w;
+  w.b = b; w.p = p; w.cmax = nn_cell_budget(p); w.gbox = nn_box_blocks(p);
+  const size_t np = (size_t)b * p, nc = (size_t)b * w.cmax + 1;
+  size_t o = 0;
+  w.part = (NnBoxPart*)(base + o); o += nn_al((size_t)b * w.gbox * sizeof(NnBoxPart));
+  w.grid = (NnGrid*)(base + o); o += nn_al((size_t)b * sizeof(NnGrid));
+  w.cnt = (int*)(base + o); o += nn_al(nc * 4);
+  w.start = (int*)(base + o); o += nn_al(nc * 4);
+  w.key = (int*)(base + o); o += nn_al(np * 4);
+  w.rank = (int*)(base + o); o += nn_al(np * 4);
+  w.sorted = (float4*)(base + o); o += nn_al(np * sizeof(float4));
+  size_t tb = 0;
+  rocprim::exclusive_scan(nullptr, tb, (int*)nullptr, (int*)nullptr, 0, nc, rocprim::plus<int>(), (hipStream_t)0);
+  w.scan_bytes = tb;
+  w.scan_tmp = (void*)(base + o); o += nn_al(tb > 0 ? tb : 1);
+  w.total = o;
+  return w;
+}
+
+__device__ __forceinline__ bool nn_finite3(float x, float y, float z) {
+  return fabsf(x) <= 3.402823466e+38f && fabsf(y) <= 3.402823466e+38f && fabsf(z) <= 3.402823466e+38f;
+}
+
+// grid (gbox, B): partial box of the finite points of item blockIdx.y, and the count of points with a non-finite coordinate
+__global__ void __launch_bounds__(kNnThreads) k_nn_box(int P, int gbox, const float* __restrict__ pts, NnBoxPart* __restrict__ part) {
+  __shared__ float red[kNnThreads / 64][6];
+  __shared__ int redb[kNnThreads / 64];
+  const int item = blockIdx.y;
+  const float* X = pts + (size_t)item * P * 3;
+  float lo0 = INFINITY, lo1 = INFINITY, lo2 = INFINITY, hi0 = -INFINITY, hi1 = -INFINITY, hi2 = -INFINITY;
+  int bad = 0;
+  for (int i = blockIdx.x * kNnThreads + threadIdx.x; i < P; i += gbox * kNnThreads) {
+    const float x = X[3 * (size_t)i], y = X[3 * (size_t)i + 1], z = X[3 * (size_t)i + 2];
+    if (nn_finite3(x, y, z)) {
+      lo0 = fminf(lo0, x); lo1 = fminf(lo1, y); lo2 = fminf(lo2, z);
+      hi0 = fmaxf(hi0, x); hi1 = fmaxf(hi1, y); hi2 = fmaxf(hi2, z);
+    } else {
+      ++bad;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    lo0 = fminf(lo0, __shfl_xor(lo0, o, 64)); lo1 = fminf(lo1, __shfl_xor(lo1, o, 64)); lo2 = fminf(lo2, __shfl_xor(lo2, o, 64));
+    hi0 = fmaxf(hi0, __shfl_xor(hi0, o, 64)); hi1 = fmaxf(hi1, __shfl_xor(hi1, o, 64)); hi2 = fmaxf(hi2, __shfl_xor(hi2, o, 64));
+    bad += __shfl_xor(bad, o, 64);
+  }
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    red[wave][0] = lo0; red[wave][1] = lo1; red[wave][2] = lo2; red[wave][3] = hi0; red[wave][4] = hi1; red[wave][5] = hi2;
+    redb[wave] = bad;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    NnBoxPart r;
+    for (int k = 0; k < 3; ++k) {
+      r.lo[k] = fminf(fminf(red[0][k], red[1][k]), fminf(red[2][k], red[3][k]));
+      r.hi[k] = fmaxf(fmaxf(red[0][3 + k], red[1][3 + k]), fmaxf(red[2][3 + k], red[3][3 + k]));
+    }
+    r.bad = redb[0] + redb[1] + redb[2] + redb[3];
+    r.pad = 0;
+    part[(size_t)item * gbox + blockIdx.x] = r;
+  }
+}
+
+// one thread per item: the box, then the cells.  An axis shorter than the cubic cell edge h (zero extent included) gets one
+// cell and h is recomputed over the other axes; then n_i = floor(e_i / h), so n0 n1 n2 <= cmax.
+__global__ void __launch_bounds__(64) k_nn_grid(int B, int gbox, int cmax, const NnBoxPart* __restrict__ part, NnGrid* __restrict__ grid) {
+  const int item = blockIdx.x * 64 + threadIdx.x;
+  if (item >= B) return;
+  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  int bad = 0;
+  for (int g = 0; g < gbox; ++g) {
+    const NnBoxPart& r = part[(size_t)item * gbox + g];
+    for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], r.lo[k]); hi[k] = fmaxf(hi[k], r.hi[k]); }
+    bad += r.bad;
+  }
+  NnGrid G;
+  double e[3];
+  bool active[3];
+  for (int k = 0; k < 3; ++k) {
+    if (!(lo[k] <= hi[k])) { lo[k] = 0.f; hi[k] = 0.f; }        // no finite point at all
+    G.o[k] = (double)lo[k];
+    G.hi[k] = (double)hi[k];
+    e[k] = (double)hi[k] - (double)lo[k];
+    active[k] = e[k] > 0.0;
+  }
+  double h = 0.0;
+  for (int it = 0; it < 3; ++it) {
+    int d = 0;
+    double vol = 1.0;
+    for (int k = 0; k < 3; ++k)
+      if (active[k]) { ++d; vol *= e[k]; }
+    if (d == 0) break;
+    h = pow(vol / (double)cmax, 1.0 / d);
+    bool changed = false;
+    for (int k = 0; k < 3; ++k)
+      if (active[k] && e[k] < h) { active[k] = false; changed = true; }
+    if (!changed) break;
+  }
+  int64_t prod = 1;
+  for (int k = 0; k < 3; ++k) {
+    double nk = active[k] && h > 0.0 ? floor(e[k] / h) : 1.0;
+    nk = fmin(fmax(nk, 1.0), (double)cmax);
+    G.n[k] = (int)nk;
+    prod *= G.n[k];
+  }
+  while (prod > cmax) {                                          // (pow's rounding) shrink the longest axis until within budget
+    int k = G.n[0] >= G.n[1] ? (G.n[0] >= G.n[2] ? 0 : 2) : (G.n[1] >= G.n[2] ? 1 : 2);
+    G.n[k] -= G.n[k] / 64 > 1 ? G.n[k] / 64 : 1;
+    prod = (int64_t)G.n[0] * G.n[1] * G.n[2];
+  }
+  for (int k = 0; k < 3; ++k) {
+    G.inv_h[k] = e[k] > 0.0 ? (double)G.n[k] / e[k] : 0.0;
+    G.h[k] = e[k] / (double)G.n[k];
+    G.slack[k] = 1e-9 * (fabs(G.o[k]) + fabs(G.hi[k])) + 1e-300;
+  }
+  G.bad = bad;
+  grid[item] = G;
+}
+
+__device__ __forceinline__ int nn_cell(double x, double o, double inv_h, int n) {
+  double f = floor((x - o) * inv_h);
+  f = fmin(fmax(f, 0.0), (double)(n - 1));      // NaN -> 0: every input lands in a cell of the grid
+  return (int)f;
+}
+
+__device__ __forceinline__ int nn_key(const NnGrid& G, float x, float y, float z) {
+  const int cx = nn_cell(x, G.o[0], G.inv_h[0], G.n[0]);
+  const int cy = nn_cell(y, G.o[1], G.inv_h[1], G.n[1]);
+  const int cz = nn_cell(z, G.o[2], G.inv_h[2], G.n[2]);
+  return (cx * G.n[1] + cy) * G.n[2] + cz;
+}
+
+// grid (ceil(P / 256), B)
+__global__ void __launch_bounds__(kNnThreads) k_nn_count(int P, int cmax, const float* __restrict__ pts, const NnGrid* __restrict__ grid,
+                                                         int* __restrict__ cnt, int* __restrict__ key, int* __restrict__ rank) {
+  const int i = blockIdx.x * kNnThreads + threadIdx.x;
+  if (i >= P) return;
+  const int item = blockIdx.y;
+  const size_t gi = (size_t)item * P + i;
+  const NnGrid& G = grid[item];
+  const int k = nn_key(G, pts[3 * gi], pts[3 * gi + 1], pts[3 * gi + 2]);
+  key[gi] = k;
+  rank[gi] = atomicAdd(&cnt[(size_t)item * cmax + k], 1);
+}
+
+__global__ void __launch_bounds__(kNnThreads) k_nn_scatter(int P, int cmax, const float* __restrict__ pts, const int* __restrict__ start,
+                                                           const int* __restrict__ key, const int* __restrict__ rank,
+                                                           float4* __restrict__ sorted) {
+  const int i = blockIdx.x * kNnThreads + threadIdx.x;
+  if (i >= P) return;
+  const int item = blockIdx.y;
+  const size_t gi = (size_t)item * P + i;
+  const int pos = start[(size_t)item * cmax + key[gi]] + rank[gi];
+  sorted[pos] = make_float4(pts[3 * gi], pts[3 * gi + 1], pts[3 * gi + 2], __int_as_float(i));
+}
+
+// squared distance in fp64, summed x, y, z without contraction (cKDTree's order)
+__device__ __forceinline__ double nn_d2(double qx, double qy, double qz, const float4& t) {
+  const double dx = qx - (double)t.x, dy = qy - (double)t.y, dz = qz - (double)t.z;
+  return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+}
+
+__device__ __forceinline__ void nn_scan_range(const float4* __restrict__ T, int s, int e, double qx, double qy, double qz, double& best,
+                                              int& bi) {
+  for (int k = s; k < e; ++k) {
+    const float4 t = T[k];
+    const double d = nn_d2(qx, qy, qz, t);
+    const int j = __float_as_int(t.w);
+    if (d < best || (d == best && j < bi)) { best = d; bi = j; }
+  }
+}
+
+// squared distance from q to the interval [lo - s, hi + s] along one axis
+__device__ __forceinline__ double nn_out2(double q, double lo, double hi, double s) {
+  const double g = q < lo - s ? (lo - s) - q : (q > hi + s ? q - (hi + s) : 0.0);
+  return g * g;
+}
+
+// grid (ceil(N / 256), B): thread t takes the t-th query of the query cloud's cell order of item blockIdx.y
+__global__ void __launch_bounds__(kNnThreads) k_nn_search(int N, int cmax_t, const float4* __restrict__ qsorted,
+                                                          const NnGrid* __restrict__ tgrid, const int* __restrict__ tstart,
+                                                          const float4* __restrict__ tsorted, int64_t* __restrict__ idx_out,
+                                                          double* __restrict__ d2_out) {
+  const int t = blockIdx.x * kNnThreads + threadIdx.x;
+  if (t >= N) return;
+  const int item = blockIdx.y;
+  const float4 q = qsorted[(size_t)item * N + t];
+  const int qi = __float_as_int(q.w);
+  const NnGrid& G = tgrid[item];
+  const int* S = tstart + (size_t)item * cmax_t;
+  double best = INFINITY;
+  int bi = INT_MAX;
+  if (nn_finite3(q.x, q.y, q.z)) {
+    const double qv[3] = {(double)q.x, (double)q.y, (double)q.z};
+    const int n0 = G.n[0], n1 = G.n[1], n2 = G.n[2];
+    int c[3];
+    double out2[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      c[k] = nn_cell(qv[k], G.o[k], G.inv_h[k], G.n[k]);
+      out2[k] = nn_out2(qv[k], G.o[k], G.hi[k], G.slack[k]);
+    }
+    const int rmax = max(n0, max(n1, n2));
+    for (int r = 0; r < rmax; ++r) {
+      int lo[3], hi[3], plo[3], phi[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        lo[k] = max(c[k] - r, 0); hi[k] = min(c[k] + r, G.n[k] - 1);
+        plo[k] = max(c[k] - r + 1, 0); phi[k] = min(c[k] + r - 1, G.n[k] - 1);   // the block of shell r - 1 (empty at r = 0)
+      }
+      for (int x = lo[0]; x <= hi[0]; ++x) {
+        const bool xin = r > 0 && x >= plo[0] && x <= phi[0];
+        for (int y = lo[1]; y <= hi[1]; ++y) {
+          const int base = (x * n1 + y) * n2;       // the cells of one (x, y) column are contiguous in the sorted cloud
+          if (!(xin && y >= plo[1] && y <= phi[1])) {
+            nn_scan_range(tsorted, S[base + lo[2]], S[base + hi[2] + 1], qv[0], qv[1], qv[2], best, bi);
+          } else {
+            if (lo[2] < plo[2]) nn_scan_range(tsorted, S[base + lo[2]], S[base + lo[2] + 1], qv[0], qv[1], qv[2], best, bi);
+            if (hi[2] > phi[2]) nn_scan_range(tsorted, S[base + hi[2]], S[base + hi[2] + 1], qv[0], qv[1], qv[2], best, bi);
+          }
+        }
+      }
+      // lower bound on the squared distance to every unvisited cell: such a cell lies beyond one face of the block, inside the box
+      double lb2 = INFINITY;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const double side = out2[(k + 1) % 3] + out2[(k + 2) % 3];
+        if (lo[k] > 0) {
+          const double g = fmax(qv[k] - (G.o[k] + lo[k] * G.h[k]) - G.slack[k], 0.0);
+          lb2 = fmin(lb2, g * g + side);
+        }
+        if (hi[k] < G.n[k] - 1) {
+          const double g = fmax((G.o[k] + (hi[k] + 1) * G.h[k]) - G.slack[k] - qv[k], 0.0);
+          lb2 = fmin(lb2, g * g + side);
+        }
+      }
+      if (best <= lb2) break;
+    }
+  }
+  const size_t o = (size_t)item * N + qi;
+  idx_out[o] = bi == INT_MAX ? 0 : (int64_t)bi;
+  if (d2_out) d2_out[o] = bi == INT_MAX ? (double)NAN : best;
+}
+
+// grid (gmean, B): fixed-order partial sums of d2 over the queries in their original order
+__global__ void __launch_bounds__(kNnThreads) k_nn_mean_part(int N, int gmean, const double* __restrict__ d2, double* __restrict__ part) {
+  __shared__ double red[kNnThreads / 64];
+  const int item = blockIdx.y;
+  const double* D = d2 + (size_t)item * N;
+  double acc = 0.0;
+  for (int i = blockIdx.x * kNnThreads + threadIdx.x; i < N; i += gmean * kNnThreads) acc += D[i];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) part[(size_t)item * gmean + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// one workgroup: wave w finishes items w, w + 4, ...  mean = sum / N, NaN where either cloud of the item is non-finite
+__global__ void __launch_bounds__(kNnThreads) k_nn_mean_finish(int B, int N, int gmean, const double* __restrict__ part,
+                                                               const NnGrid* __restrict__ ga, const NnGrid* __restrict__ gb,
+                                                               double* __restrict__ out) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int item = wave; item < B; item += kNnThreads / 64) {
+    double acc = 0.0;
+    for (int j = lane; j < gmean; j += 64) acc += part[(size_t)item * gmean + j];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if (lane == 0) out[item] = (ga[item].bad || gb[item].bad) ? (double)NAN : acc / (double)N;
+  }
+}
+
+static int nn_bin(const NnBin& w, const float* pts, hipStream_t s) {
+  NM_LAUNCH(k_nn_box, dim3(w.gbox, w.b), dim3(kNnThreads), 0, s, w.p, w.gbox, pts, w.part);
+  NM_LAUNCH_CHECK();
+  NM_LAUNCH(k_nn_grid, dim3(nm_div_up(w.b, 64)), dim3(64), 0, s, w.b, w.gbox, w.cmax, (const NnBoxPart*)w.part, w.grid);
+  NM_LAUNCH_CHECK();
+  const size_t nc = (size_t)w.b * w.cmax + 1;
+  NM_HIP_CHECK(hipMemsetAsync(w.cnt, 0, nc * sizeof(int), s));
+  const dim3 pg(nm_div_up(w.p, kNnThreads), w.b);
+  NM_LAUNCH(k_nn_count, pg, dim3(kNnThreads), 0, s, w.p, w.cmax, pts, (const NnGrid*)w.grid, w.cnt, w.key, w.rank);
+  NM_LAUNCH_CHECK();
+  size_t tb = w.scan_bytes;
+  NM_HIP_CHECK(rocprim::exclusive_scan(w.scan_tmp, tb, w.cnt, w.start, 0, nc, rocprim::plus<int>(), s));
+  NM_LAUNCH(k_nn_scatter, pg, dim3(kNnThreads), 0, s, w.p, w.cmax, pts, (const int*)w.start, (const int*)w.key, (const int*)w.rank,
+            w.sorted);
+  NM_LAUNCH_CHECK();
+  return NM_OK;
+}
+
+static int nn_search(const NnBin& q, const NnBin& t, int64_t* idx, double* d2, hipStream_t s) {
+  NM_LAUNCH(k_nn_search, dim3(nm_div_up(q.p, kNnThreads), q.b), dim3(kNnThreads), 0, s, q.p, t.cmax, (const float4*)q.sorted,
+            (const NnGrid*)t.grid, (const int*)t.start, (const float4*)t.sorted, idx, d2);
+  NM_LAUNCH_CHECK();
+  return NM_OK;
+}
+
+static int nn_mean(const NnBin& q, const NnBin& t, const double* d2, double* part, double* out, hipStream_t s) {
+  const int gm = nn_mean_blocks(q.p);
+  NM_LAUNCH(k_nn_mean_part, dim3(gm, q.b), dim3(kNnThreads), 0, s, q.p, gm, d2, part);
+  NM_LAUNCH_CHECK();
+  NM_LAUNCH(k_nn_mean_finish, dim3(1), dim3(kNnThreads), 0, s, q.b, q.p, gm, (const double*)part, (const NnGrid*)q.grid,
+            (const NnGrid*)t.grid, out);
+  NM_LAUNCH_CHECK();
+  return NM_OK;
+}
+
+static bool nn_sizes_ok(int32_t b, int32_t n1, int32_t n2) {
+  return b >= 1 && b <= 65535 && n1 >= 1 && n2 >= 1 && (int64_t)b * n1 < INT32_MAX && (int64_t)b * n2 < INT32_MAX;
+}
+
+struct ChamferWs {
+  NnBin a, b;
+  double *d2a, *d2b, *part;
+  size_t total;
+};
+
+static ChamferWs carve_chamfer(char* base, int b, int n1, int n2) {
+  ChamferWs w;
+  size_t o = 0;
+  w.a = carve_bin(base + o, b, n1); o += w.a.total;
+  w.b = carve_bin(base + o, b, n2); o += w.b.total;
+  w.d2a = (double*)(base + o); o += nn_al((size_t)b * n1 * sizeof(double));
+  w.d2b = (double*)(base + o); o += nn_al((size_t)b * n2 * sizeof(double));
+  w.part = (double*)(base + o); o += nn_al((size_t)b * (nn_mean_blocks(n1) + nn_mean_blocks(n2)) * sizeof(double));
+  w.total = o;
+  return w;
+}
+
+}  // namespace
+
+extern "C" size_t nm_nn_workspace(int32_t b, int32_t n_query, int32_t n_target) {
+  if (!nn_sizes_ok(b, n_query, n_target)) return 0;
+  const NnBin q = carve_bin(nullptr, b, n_query);
+  return q.total + carve_bin(nullptr, b, n_target).total;
+}
+
+extern "C" int nm_nearest_neighbors(int32_t b, int32_t n_query, int32_t n_target, const float* query, const float* target,
+                                    int64_t* idx_out, double* d2_out, void* ws, size_t ws_bytes, void* stream) {
+  NM_REQUIRE(b >= 1 && b <= 65535, "b must be in [1, 65535]");
+  NM_REQUIRE(n_query >= 1 && n_target >= 1, "empty point cloud");
+  NM_REQUIRE(nn_sizes_ok(b, n_query, n_target), "b * points above 2^31 - 1");
+  NM_REQUIRE(query && target && idx_out && ws, "null pointer");
+  NM_REQUIRE(ws_bytes >= nm_nn_workspace(b, n_query, n_target), "workspace too small (nm_nn_workspace)");
+  const hipStream_t s = (hipStream_t)stream;
+  const NnBin q = carve_bin((char*)ws, b, n_query);
+  const NnBin t = carve_bin((char*)ws + q.total, b, n_target);
+  int rc;
+  if ((rc = nn_bin(q, query, s)) != NM_OK) return rc;
+  if ((rc = nn_bin(t, target, s)) != NM_OK) return rc;
+  return nn_search(q, t, idx_out, d2_out, s);
+}
+
+extern "C" size_t nm_chamfer_workspace(int32_t b, int32_t n1, int32_t n2) {
+  if (!nn_sizes_ok(b, n1, n2)) return 0;
+  return carve_chamfer(nullptr, b, n1, n2).total;
+}
+
+extern "C" int nm_chamfer(int32_t b, int32_t n1, int32_t n2, const float* p1, const float* p2, double* cd12_out, double* cd21_out,
+                          int64_t* idx12, int64_t* idx21, void* ws, size_t ws_bytes, void* stream) {
+  NM_REQUIRE(b >= 1 && b <= 65535, "b must be in [1, 65535]");
+  NM_REQUIRE(n1 >= 1 && n2 >= 1, "empty point cloud");
+  NM_REQUIRE(nn_sizes_ok(b, n1, n2), "b * points above 2^31 - 1");
+  NM_REQUIRE(p1 && p2 && cd12_out && cd21_out && ws, "null pointer");
+  NM_REQUIRE(ws_bytes >= nm_chamfer_workspace(b, n1, n2), "workspace too small (nm_chamfer_workspace)");
+  const hipStream_t s = (hipStream_t)stream;
+  const ChamferWs w = carve_chamfer((char*)ws, b, n1, n2);
+  // without caller arrays the indices go to the (then unused) key arrays' space: B * n int64 = the key + rank arrays
+  int64_t* i12 = idx12 ? idx12 : (int64_t*)w.a.key;
+  int64_t* i21 = idx21 ? idx21 : (int64_t*)w.b.key;
+  int rc;
+  if ((rc = nn_bin(w.a, p1, s)) != NM_OK) return rc;
+  if ((rc = nn_bin(w.b, p2, s)) != NM_OK) return rc;
+  if ((rc = nn_search(w.a, w.b, i12, w.d2a, s)) != NM_OK) return rc;
+  if ((rc = nn_search(w.b, w.a, i21, w.d2b, s)) != NM_OK) return rc;
+  if ((rc = nn_mean(w.a, w.b, w.d2a, w.part, cd12_out, s)) != NM_OK) return rc;
+  return nn_mean(w.b, w.a, w.d2b, w.part + (size_t)b * nn_mean_blocks(n1), cd21_out, s);
+}
