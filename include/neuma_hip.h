@@ -578,6 +578,19 @@ size_t nm_chamfer_workspace(int32_t b, int32_t n1, int32_t n2);
 int nm_chamfer(int32_t b, int32_t n1, int32_t n2, const float* p1, const float* p2, double* cd12_out, double* cd21_out,
                int64_t* idx12, int64_t* idx21, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ mesh sampling (particles inside a triangle mesh) */
+
+/* Ray-parity inside test of a triangle mesh, bit for bit the fp64 formula of extras/mesh_sampling.py points_in_mesh applied to
+ * points that ALREADY carry its ray offset: verts (n_verts, 3) fp64, tris (n_tris, 3) int32, points (n_points, 3) fp64, all
+ * contiguous on the device.  Triangles with |d| <= 1e-300 (d = twice the signed xy area) or a vertex index outside
+ * [0, n_verts) are dropped (an out-of-range vertex is never read).  inside_out[i] (DEVICE, uint8) = 1 when the number of
+ * triangles with barycentrics l0, l1, l2 >= 0 at the point's xy and interpolated z > the point's z is odd.  No float atomics,
+ * no host synchronisation: two calls give identical bytes.  workspace: nm_mesh_inside_workspace(n_tris, n_points) bytes of
+ * device scratch (0 = invalid sizes).  Negative sizes, n_tris > 2^27 or a too small workspace -> -1 before any device work. */
+size_t nm_mesh_inside_workspace(int32_t n_tris, int32_t n_points);
+int nm_points_in_mesh(int32_t n_verts, int32_t n_tris, int32_t n_points, const double* verts, const int32_t* tris,
+                      const double* points, uint8_t* inside_out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,13 +2,16 @@
 
 Kept apart from the path's own readers (neuma_amd/io.py) on purpose: a convenience for running the finetune / render entry points
 on a machine that has neither trimesh nor the reference's prebuilt `VolumeSampling` binary - triangle-mesh readers (PLY / OBJ),
-volume sampling by a ray-parity inside test, and the mesh volume.  Nothing under csrc/, nothing on the frame path and no parity
-claim depends on it; prepare.py and MPMInitData.get_pcd use it only when the `.npz` particle cache the reference writes is absent."""
+volume sampling by a ray-parity inside test, and the mesh volume.  Nothing on the frame path and no parity claim depends on it.
+Its `points_in_mesh` / `sample_mesh_points` are the CPU oracle of neuma_amd/mesh_inside.py, which runs the same test on the
+GPU (csrc/nm_mesh.hip) and takes its candidates and ray offset from `mesh_candidate_points` / `ray_offset_points` here;
+prepare.py and regist.py sample with that GPU path, MPMInitData.get_pcd with this module when the `.npz` particle cache the
+reference writes is absent."""
 from typing import Tuple
 
 import numpy as np
 
-from ..io import _ply_header, _ply_vertex_block
+from ..io import _PLY_TYPES, _ply_header, _ply_vertex_block
 
 
 def read_ply_mesh(path):
@@ -32,13 +35,40 @@ def read_ply_mesh(path):
             end = "<" if fmt == "binary_little_endian" else ">"
             ct, it = (np.dtype(end + _PLY_TYPES[t]) for t in face["props"][0][2])
             extra = sum(np.dtype(p[0]).itemsize for p in face["props"][1:])       # fixed-size properties after the list
-            for _ in range(face["count"]):
+            uniform = _ply_faces_uniform(f, face["count"], ct, it, extra)
+            if uniform is not None:
+                return verts, uniform
+            for _ in range(face["count"]):                                     # faces of different sizes: one at a time
                 k = int(np.frombuffer(f.read(ct.itemsize), dtype=ct)[0])
                 idx = np.frombuffer(f.read(it.itemsize * k), dtype=it).astype(np.int64)
                 if extra:
                     f.read(extra)
                 tris += [(idx[0], idx[i], idx[i + 1]) for i in range(1, k - 1)]
         return verts, np.asarray(tris, dtype=np.int64).reshape(-1, 3)
+
+
+def _ply_faces_uniform(f, n, ct, it, extra):
+    """The binary face block in one read when every face has the same vertex count k >= 3: (n (k - 2), 3) int64 triangles,
+    fanned in the per-face loop's order.  None (and `f` back where it was) when the counts differ or the block is short."""
+    start = f.tell()
+    head = f.read(ct.itemsize)
+    f.seek(start)
+    if n < 1 or len(head) != ct.itemsize:
+        return None
+    k = int(np.frombuffer(head, dtype=ct)[0])
+    if k < 3:
+        return None
+    rec = ct.itemsize + k * it.itemsize + extra
+    raw = f.read(rec * n)
+    dt = np.dtype({"names": ["k", "idx"], "formats": [ct, (it, (k,))], "offsets": [0, ct.itemsize], "itemsize": rec})
+    arr = np.frombuffer(raw, dtype=dt, count=n) if len(raw) == rec * n else None
+    if arr is None or (arr["k"] != k).any():
+        f.seek(start)
+        return None
+    idx = arr["idx"].astype(np.int64)                                            # (n, k)
+    j = np.arange(1, k - 1)
+    tris = np.stack((np.broadcast_to(idx[:, :1], (n, k - 2)), idx[:, j], idx[:, j + 1]), axis=-1)
+    return np.ascontiguousarray(tris.reshape(-1, 3))
 
 
 def read_obj_mesh(path):
@@ -58,16 +88,20 @@ def read_obj_mesh(path):
     return np.asarray(verts, dtype=np.float64), np.asarray(tris, dtype=np.int64).reshape(-1, 3)
 
 
+def ray_offset_points(points: np.ndarray, verts: np.ndarray) -> np.ndarray:
+    """The points points_in_mesh casts its rays from: moved off the given ones by a tiny irrational offset (a grid point exactly
+    above a triangle edge would otherwise count both triangles), scaled by the mesh's largest |coordinate|."""
+    span = float(np.abs(np.asarray(verts)).max()) or 1.0
+    return np.asarray(points, dtype=np.float64) + np.array([1.2345678e-7, 2.7182818e-7, 0.0]) * span
+
+
 def points_in_mesh(points: np.ndarray, verts: np.ndarray, tris: np.ndarray) -> np.ndarray:
     """Inside test of a closed triangle mesh by ray parity along +z (counterpart of trimesh's `mesh.contains`, which the
     reference's samplers rely on, tune/utils.py:49-200).  points (n,3) -> bool (n,)."""
     p = np.asarray(points, dtype=np.float64)
     a, b, c = (np.asarray(verts, dtype=np.float64)[np.asarray(tris)[:, k]] for k in range(3))
     inside = np.zeros(len(p), dtype=bool)
-    # (the ray is moved off the point by a tiny irrational offset: a grid point exactly above a triangle edge would otherwise
-    # count both triangles)
-    span = float(np.abs(np.asarray(verts)).max()) or 1.0
-    p = p + np.array([1.2345678e-7, 2.7182818e-7, 0.0]) * span
+    p = ray_offset_points(p, verts)
     d = (b[:, 1] - c[:, 1]) * (a[:, 0] - c[:, 0]) + (c[:, 0] - b[:, 0]) * (a[:, 1] - c[:, 1])       # 2 x signed area in xy
     ok = np.abs(d) > 1e-300
     a, b, c, d = a[ok], b[ok], c[ok], d[ok]
@@ -87,6 +121,13 @@ def sample_mesh_points(verts: np.ndarray, tris: np.ndarray, mode: str = "volumet
     """Particles inside a closed mesh (tune/utils.py:49-200 without trimesh / the prebuilt VolumeSampling binary):
     'volumetric' = the points of a regular grid with `resolution` cells along the longest side of the bounding box that lie
     inside; 'uniform' = resolution^3 uniformly random points of the bounding box, those inside kept."""
+    pts = mesh_candidate_points(verts, mode, resolution, seed)
+    return pts[points_in_mesh(pts, verts, tris)]
+
+
+def mesh_candidate_points(verts: np.ndarray, mode: str = "volumetric", resolution: int = 30, seed: int = 0) -> np.ndarray:
+    """The candidates sample_mesh_points tests, in its order (the 'volumetric' lattice in ij order, or the seeded 'uniform'
+    points)."""
     lo, hi = verts.min(0), verts.max(0)
     if mode == "volumetric":
         h = float((hi - lo).max()) / int(resolution)
@@ -96,7 +137,7 @@ def sample_mesh_points(verts: np.ndarray, tris: np.ndarray, mode: str = "volumet
         pts = lo + (hi - lo) * np.random.default_rng(seed).random((int(resolution) ** 3, 3))
     else:
         raise ValueError(f"mesh_sample_mode '{mode}' is not available here (volumetric / uniform)")
-    return pts[points_in_mesh(pts, verts, tris)]
+    return pts
 
 
 def mesh_volume(verts: np.ndarray, tris: np.ndarray) -> float:

@@ -7,14 +7,16 @@ it writes, into experiments/assets/<sim_data_name>/:
     bindings.pt     sparse (K x N) binding weights + per-Gaussian particle counts
 The O(K N) Mahalanobis loop of binding_utils.py runs as the grid-hashed HIP search of neuma_amd.binding.
 Particles out of a mesh (particle_data.mesh_path, tune/utils.py:49-200): 'volumetric' / 'uniform' are sampled here with a
-ray-parity inside test (io.sample_mesh_points; the reference calls trimesh and a prebuilt `VolumeSampling` ELF); a
-particles.ply already lying in the asset folder is used as it is."""
+ray-parity inside test (mesh_inside.sample_mesh_points on a GPU device, extras.mesh_sampling's on the CPU - the same
+particles; the reference calls trimesh and a prebuilt `VolumeSampling` ELF); a particles.ply already lying in the asset folder
+is used as it is."""
 from pathlib import Path
 from typing import Optional
 
 import torch
 
 from . import io as nio
+from . import mesh_inside
 from .extras import mesh_sampling as mesh      # (outside the section-8 scope: see its header)
 from .binding import prepare_bindings
 
@@ -49,7 +51,12 @@ def prepare_simulation_data(save_dir: Path, kernels_path: Path, particles_path: 
     elif mesh_path is not None:
         print(f"Sampling particles inside mesh [{mesh_path}] ({mesh_sample_mode}, resolution {mesh_sample_resolution}) ...")
         reader = mesh.read_obj_mesh if Path(mesh_path).suffix.lower() == ".obj" else mesh.read_ply_mesh
-        particles = mesh.sample_mesh_points(*reader(mesh_path), mode=mesh_sample_mode, resolution=int(mesh_sample_resolution))
+        verts, tris = reader(mesh_path)
+        if torch.device(device).type == "cuda":
+            particles = mesh_inside.sample_mesh_points(verts, tris, mode=mesh_sample_mode, resolution=int(mesh_sample_resolution),
+                                                       device=device)
+        else:
+            particles = mesh.sample_mesh_points(verts, tris, mode=mesh_sample_mode, resolution=int(mesh_sample_resolution))
         particles_downsample_factor = 1
     else:
         raise ValueError("Either 'particles_path' or 'mesh_path' must be provided.")

@@ -473,11 +473,14 @@ def regist_gaussians(cfg, log=print) -> Optional[float]:
     return ema
 
 
-def regist_particles(cfg, log=print) -> np.ndarray:
-    """regist.py:208-247 with the project's mesh sampler (extras.mesh_sampling; 'surface' needs trimesh: unavailable)."""
+def regist_particles(cfg, log=print, device=None) -> np.ndarray:
+    """regist.py:208-247 with the project's mesh sampler ('surface' needs trimesh: unavailable): mesh_inside on a GPU
+    `device` (default cuda:<cfg.gpu>, as regist_gaussians), extras.mesh_sampling otherwise - the same particles."""
     import shutil
     from . import io as nio
+    from . import mesh_inside
     from .extras import mesh_sampling as mesh
+    device = torch.device(device if device is not None else f"cuda:{cfg.get('gpu', 0)}")
     save_dir = _assets_root(cfg) / cfg.sim_data_name
     out = save_dir / "registered_particles.ply"
     if out.is_file():
@@ -492,7 +495,11 @@ def regist_particles(cfg, log=print) -> np.ndarray:
         shutil.copyfile(mesh_path, save_dir / f"mesh{mesh_path.suffix}")
         reader = mesh.read_obj_mesh if mesh_path.suffix.lower() == ".obj" else mesh.read_ply_mesh
         mode = cfg.particle_data.get("mesh_sample_mode", "volumetric")
-        particles = mesh.sample_mesh_points(*reader(mesh_path), mode=mode, resolution=int(cfg.particle_data["mesh_sample_resolution"]))
+        res = int(cfg.particle_data["mesh_sample_resolution"])
+        if device.type == "cuda":
+            particles = mesh_inside.sample_mesh_points(*reader(mesh_path), mode=mode, resolution=res, device=device)
+        else:
+            particles = mesh.sample_mesh_points(*reader(mesh_path), mode=mode, resolution=res)
         tr = np.load(save_dir / "registered_params.npz")
         pts = transform_pcd(particles, tr["s"], tr["o"], tr["r"], tr["t"])
         nio.save_particles_ply(out, pts)
