@@ -591,6 +591,34 @@ size_t nm_mesh_inside_workspace(int32_t n_tris, int32_t n_points);
 int nm_points_in_mesh(int32_t n_verts, int32_t n_tris, int32_t n_points, const double* verts, const int32_t* tris,
                       const double* points, uint8_t* inside_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ classical constitutive laws (material/classical.py) */
+
+/* The closed-form laws of the reference's nclaw/material/preset.py:30-282, one thread per particle.  `law`: */
+#define NM_LAW_COROTATED 0      /* stress  2 mu (F - U Vh) F^T + la J (J - 1) I,  J = prod(sigma) */
+#define NM_LAW_STVK 1           /* stress  mu F (F^T F - I) + la J (J - 1) I,     J = prod(sigma) */
+#define NM_LAW_VOLUME 2         /* stress  mode 0 (ziran): kappa (J - 1 / J) I;  mode 1 (taichi): la J (J - 1) I;  J = det F */
+#define NM_LAW_SIGMA 3          /* stress  U diag(2 mu log sigma + la tr log sigma) U^T (NaN where a sigma is negative) */
+#define NM_LAW_IDENTITY 4       /* F       a device-to-device copy, no kernel */
+#define NM_LAW_SIGMA_PLASTIC 5  /* F       diag(det(F)^(1/3)) (NaN where det F < 0) */
+#define NM_LAW_VON_MISES 6      /* F       sigma clamped at 0.05, return map where |dev log sigma| > sigma_y / (2 mu), else F */
+#define NM_LAW_DRUCKER_PRAGER 7 /* F       sigma clamped at 0.05; cone projection where tr log sigma < 3 cohesion, else exp(cohesion) U Vh */
+#define NM_VOLUME_ZIRAN 0
+#define NM_VOLUME_TAICHI 1
+/* scalars (DEVICE, 4 floats, read by the kernel - no host copy): {log_E, nu, p2, p3} with p2 = sigma_y (law 6) or the friction
+ * angle in degrees (law 7) and p3 = cohesion (law 7); unused entries are ignored (laws 4, 5 accept NULL).  F, out: (n, 3, 3)
+ * fp32 row-major.  The SVD is nm_svd3_fwd's.  Both branches of a switch are evaluated and selected, so a row with
+ * |dev log sigma| = 0 gives what the reference gives (NaN on the yielding side of law 7). */
+int nm_classical_fwd(int32_t n, int32_t law, int32_t mode, const float* scalars, const float* F, float* out, void* stream);
+/* Adjoint: grad_F (n, 3, 3), and grad_scalars (DEVICE, 2 floats, OVERWRITTEN: {d/d log_E, d/d p2}; may be NULL for laws 4, 5)
+ * summed over the particles as fp64 per-block partials and one fixed-order block (no float atomics: two calls give the same
+ * bits).  The SVD is recomputed; its adjoint is nm_svd3_bwd's clamped form.  Where a switch picks the other branch that
+ * branch's gradient is dropped by a select, not multiplied by zero: a non-yielding von Mises row with |dev log sigma| = 0
+ * returns grad_out (the reference returns NaN there).  Non-finite values are passed on unchanged.
+ * workspace: nm_classical_bwd_workspace(n) bytes of device scratch (0 for n <= 0). */
+size_t nm_classical_bwd_workspace(int32_t n);
+int nm_classical_bwd(int32_t n, int32_t law, int32_t mode, const float* scalars, const float* F, const float* grad_out,
+                     float* grad_F, float* grad_scalars, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

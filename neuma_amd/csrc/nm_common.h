@@ -261,6 +261,27 @@ NM_HD void nm_svd3(const M3& A, M3& U, float s[3], M3& Vm) {
   for (int i = 0; i < 9; ++i) Vm.m[i] = V[i];
 }
 
+// adjoint of nm_svd3 with the clamped denominators of warp's adj_svd3: gF from (gU, gs, gVh).
+// E_ab = 1 / min(s_b^2 - s_a^2, -1e-6) for a < b.
+NM_HD M3 nm_svd3_adj(const M3& Um, const float s[3], const M3& Vhm, const M3& gUm, const float g[3], const M3& gVhm) {
+  M3 UtgU = m3_mul_tn(Um, gUm);
+  M3 VtgV = m3_mul_nt(Vhm, gVhm);  // V^T gV = Vh (gVh)^T
+  M3 inner = m3_zero();
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      if (i == j) { inner.m[4 * i] = g[i]; continue; }
+      int a = i < j ? i : j, b = i < j ? j : i;
+      float e = 1.f / fminf(s[b] * s[b] - s[a] * s[a], -1e-6f);
+      if (i > j) e = -e;
+      float su = e * (UtgU.m[3 * i + j] - UtgU.m[3 * j + i]);
+      float sv = e * (VtgV.m[3 * i + j] - VtgV.m[3 * j + i]);
+      inner.m[3 * i + j] = su * s[j] + s[i] * sv;
+    }
+  return m3_mul(m3_mul(Um, inner), Vhm);
+}
+
 // wave64 sum via cross-lane shuffles (result valid in every lane)
 __device__ __forceinline__ float nm_wave_sum(float v) {
 #pragma unroll

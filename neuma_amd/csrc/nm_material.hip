@@ -172,22 +172,7 @@ __global__ void __launch_bounds__(256) k_svd_bwd(int n, const float* __restrict_
   float s[3] = {sig[3 * p], sig[3 * p + 1], sig[3 * p + 2]};
   float g[3] = {0.f, 0.f, 0.f};
   if (gs) { g[0] = gs[3 * p]; g[1] = gs[3 * p + 1]; g[2] = gs[3 * p + 2]; }
-  M3 UtgU = m3_mul_tn(Um, gUm);
-  M3 VtgV = m3_mul_nt(Vhm, gVhm);  // V^T gV = Vh (gVh)^T
-  M3 inner = m3_zero();
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      if (i == j) { inner.m[4 * i] = g[i]; continue; }
-      int a = i < j ? i : j, b = i < j ? j : i;
-      float e = 1.f / fminf(s[b] * s[b] - s[a] * s[a], -1e-6f);
-      if (i > j) e = -e;
-      float su = e * (UtgU.m[3 * i + j] - UtgU.m[3 * j + i]);
-      float sv = e * (VtgV.m[3 * i + j] - VtgV.m[3 * j + i]);
-      inner.m[3 * i + j] = su * s[j] + s[i] * sv;
-    }
-  m3_store(gF + 9 * p, m3_mul(m3_mul(Um, inner), Vhm));
+  m3_store(gF + 9 * p, nm_svd3_adj(Um, s, Vhm, gUm, g, gVhm));
 }
 
 extern "C" int nm_svd3_fwd(int32_t n, const float* F, float* U, float* sigma, float* Vh, void* stream) {

@@ -32,7 +32,7 @@ from .config import Cfg, load_config
 from .dataset import CameraDataset
 from .evaluate import save_image
 from .infer import SceneObject, simulate_objects
-from .material import InvariantFullMetaElasticity, InvariantFullMetaPlasticity
+from .material import InvariantFullMetaElasticity, InvariantFullMetaPlasticity, build as build_material
 from .prepare import prepare_simulation_data
 from .sim import MPMInitData, MPMModelBuilder
 
@@ -88,19 +88,24 @@ def load_object(obj_cfg: Cfg, assets: Path, eval_steps: int, device) -> SceneObj
     print(f"#Max particles: {float(n_particles.max())}, index: {int(torch.argmax(n_particles))}")
     gaussians = nio.load_gaussians_ply(data_root / "kernels.ply", gc.sh_degree, device=device)
     cc = obj_cfg.constitution
-    elasticity = InvariantFullMetaElasticity(cc.elasticity).to(device)
-    plasticity = InvariantFullMetaPlasticity(cc.plasticity).to(device)
-    pretrained = torch.load(obj_cfg.pretrained_ckpt, map_location=device)
-    elasticity.load_state_dict(pretrained["elasticity"])
-    plasticity.load_state_dict(pretrained["plasticity"])
-    print(f"Loaded pretrained weights from {obj_cfg.pretrained_ckpt}")
-    if cc.get("load_lora") is not None:
-        elasticity.init_lora_layers(r=cc.lora.r, lora_alpha=cc.lora.alpha)
-        plasticity.init_lora_layers(r=cc.lora.r, lora_alpha=cc.lora.alpha)
+    # an optional `name` in a constitution block picks a classical law (material/classical.py), which takes its constants from
+    # the block itself; without it the block is the neural net of the checkpoint, as in the reference
+    elasticity = build_material(cc.elasticity, InvariantFullMetaElasticity).to(device)
+    plasticity = build_material(cc.plasticity, InvariantFullMetaPlasticity).to(device)
+    nets = [(k, m) for k, m in (("elasticity", elasticity), ("plasticity", plasticity))
+            if isinstance(m, (InvariantFullMetaElasticity, InvariantFullMetaPlasticity))]
+    if nets:
+        pretrained = torch.load(obj_cfg.pretrained_ckpt, map_location=device)
+        for k, m in nets:
+            m.load_state_dict(pretrained[k])
+        print(f"Loaded pretrained weights from {obj_cfg.pretrained_ckpt}")
+    if nets and cc.get("load_lora") is not None:
+        for k, m in nets:
+            m.init_lora_layers(r=cc.lora.r, lora_alpha=cc.lora.alpha)
         lora = torch.load(cc.load_lora, map_location=device)
-        elasticity.load_state_dict(lora["elasticity"], strict=False)
-        plasticity.load_state_dict(lora["plasticity"], strict=False)
-        elasticity.to(device); plasticity.to(device)
+        for k, m in nets:
+            m.load_state_dict(lora[k], strict=False)
+            m.to(device)
         print(f"Loaded lora weights from {cc.load_lora}")
     pd.span = [0, eval_steps]                                   # NOTE: manually setting (inference.py:234)
     pd.shape.name = obj_cfg.sim_data_name + "/particles"        # NOTE: manually setting (inference.py:235)

@@ -1,11 +1,15 @@
 """ComposeMaterial — per-object split / apply / concatenate.
-Mirrors /root/reference/modules/nclaw/material/preset.py:12-27 (the classical presets of that file are never
-instantiated by any NeuMA driver and are out of scope)."""
+Mirrors /root/reference/modules/nclaw/material/preset.py:12-27.  The classical presets of that file (:30-282) live in
+classical.py on their own HIP kernels and are re-exported here under the reference's names, so
+`from neuma_amd.material.preset import CorotatedElasticity` works as there."""
 from typing import Sequence
 
 import torch
 import torch.nn as nn
 from torch import Tensor
+
+from .classical import (CorotatedElasticity, StVKElasticity, VolumeElasticity, SigmaElasticity, IdentityPlasticity,  # noqa: F401
+                        SigmaPlasticity, VonMisesPlasticity, DruckerPragerPlasticity)
 
 
 class ComposeMaterial(nn.Module):
