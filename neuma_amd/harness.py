@@ -14,6 +14,7 @@ steps its contiguous range of the particle list and the ranks all-reduce the gri
 per substep; positions and deformation gradients are all-gathered once per frame for the bindings, and the LoRA
 gradients are summed over the ranks after the backward pass.
 """
+import contextlib
 import os
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
@@ -239,22 +240,9 @@ def _tail_backward(rt, recs, grads, streams, dx_out, outs=None, scale=1.0):
 _LAST_GF_ZERO = 0 if os.environ.get("NEUMA_LAST_GF_ZERO", "1") == "0" else 1
 
 
-def _status_words_out(rt, lib, gptr, cfg, status, ev, gcache):
-    """The grid cache records' status words on their way to pinned memory behind the forward sweep, `ev` recorded behind them.
-    The library writes them from a one-wave kernel straight into the pinned words (nm_rollout_cache_status): the strided
-    device-to-host copy it replaces was a 20 us hole on the frame's stream between the roll-out and the frame's tail.
-    (Round 5 also tried the copy on a stream of its own: neutral for the single frame, -5 % for the epoch - a fifth stream
-    shares a hardware queue with one of the four the epoch already uses.)"""
-    import ctypes as C
-    from . import _lib as L
-    L.check(lib.nm_rollout_cache_status(gptr, C.byref(cfg), C.c_void_p(status.data_ptr()), L.stream_ptr(rt.device)), "nm_rollout_cache_status")
-    ev.record()
-
-
 class _FrameState(object):
     """What the forward half of a one-node frame keeps for its reverse sweep."""
-    __slots__ = ("recs", "grads", "streams", "keep", "states", "eff", "gcache", "svdc", "actc", "status", "ev", "cache_blocks",
-                 "adj", "weight", "ws_token", "ws_ptr", "outs")
+    __slots__ = ("recs", "grads", "streams", "keep", "states", "eff", "call", "weight", "ws_token", "ws_ptr", "outs")
 
 
 def _frame_static(rt):
@@ -304,39 +292,19 @@ def _frame_forward(rt, weight, jobs, streams, eager=False):
     # roll-out: record 0 = the (packed) start state
     states = torch.empty(S + 1, 33 * n, dtype=torch.float32, device=dev)
     states[0, :24 * n].copy_(rt._start_packed())
-    sz = rt.__dict__.get("_roll_sizes")
-    cache_blocks = int(sim.grid_cache_blocks())
-    if sz is None or sz[0] != (n, S, cache_blocks):
-        sz = rt._roll_sizes = ((n, S, cache_blocks), int(lib.nm_rollout_workspace(n, S)),
-                               int(lib.nm_rollout_gridcache_bytes(S, cache_blocks)) if cache_blocks > 0 else 0,
-                               int(lib.nm_rollout_svdcache_bytes(n, S)), int(lib.nm_rollout_actcache_bytes(n, S)))
-    _, ws_bytes, gc_bytes, svd_bytes, act_bytes = sz
-    ws = rt._scratch("ws", ws_bytes)
-    gcache = torch.empty(gc_bytes, dtype=torch.uint8, device=dev) if gc_bytes > 0 else None
-    svdc = R.lease_cache(svd_bytes, dev) if R._SVD_CACHE else None
-    actc = R.lease_cache(act_bytes, dev, force=R._ACT_CACHE == '1') if R._ACT_CACHE != '0' else None
-    adj = L.SVD_ADJOINT[sim.svd_adjoint]
-    cfg = L.nm_rollout_cfg(S, float(sim.plasticity.alpha), cache_blocks if gcache is not None else 0, 0, adj,
-                           svdc.t.data_ptr() if svdc is not None else None, actc.t.data_ptr() if actc is not None else None, 0,
-                           _LAST_GF_ZERO)      # (the reverse sweep will say the same: see _frame_backward)
-    w0, w1 = R._WSZ[0], R._WSZ[0] + R._WSZ[1]
-    mle = L.nm_mlp(base, base + 4 * w0, base + 4 * w1)
-    pb = base + 4 * nw
-    mlp = L.nm_mlp(pb, pb + 4 * w0, pb + 4 * w1)
-    gptr = gcache.data_ptr() if gcache is not None else None
+    call = R.RolloutCall.open(lib, dev, n, S, sim.plasticity.alpha, L.SVD_ADJOINT[sim.svd_adjoint], int(sim.grid_cache_blocks()),
+                              last_gF_zero=_LAST_GF_ZERO,      # (the reverse sweep will say the same: see _frame_backward)
+                              status_pool=rt.__dict__.setdefault("_status_pool", []))
+    ws = rt._scratch("ws", call.ws_bytes)
+    cfg = call.forward_cfg()
+    mle, mlp = R.mlp_pair(base, nw)
     L.check(lib.nm_rollout_forward(rt.model.handle(), n, C.byref(cfg), C.byref(st), C.byref(mle), C.byref(mlp), states.data_ptr(),
-                                   gptr, ws.data_ptr(), ws_bytes, stream), "nm_rollout_forward")
+                                   call.gcache.data_ptr() if call.gcache is not None else None, ws.data_ptr(), call.ws_bytes, stream),
+            "nm_rollout_forward")
     fs = _FrameState()
     fs.ws_token = rt._ws_token = rt.__dict__.get("_ws_token", 0) + 1      # (whose operand-order weights the workspace holds)
     fs.ws_ptr = ws.data_ptr()
-    fs.status = fs.ev = None
-    if gcache is not None and R._CACHE_STATUS:
-        pool = rt.__dict__.setdefault("_status_pool", [])      # (pinned words + event: handed back by the backward pass)
-        if pool and pool[-1][0].numel() == S:
-            fs.status, fs.ev = pool.pop()
-        else:
-            fs.status, fs.ev = torch.empty(S, dtype=torch.int32, pin_memory=True), torch.cuda.Event()
-        _status_words_out(rt, lib, gptr, cfg, fs.status, fs.ev, gcache)
+    call.watch(lib, stream)
     if sim._cache_blocks is None:      # first roll-out: size the grid cache from what the scene touches (one host sync)
         blocks, _ = rt.model.grid_stats()
         sim._cache_blocks = int(1.5 * blocks) + 64
@@ -345,8 +313,7 @@ def _frame_forward(rt, weight, jobs, streams, eager=False):
     p_cur = x if rt._unit_frame() else ((x - rt.center) / rt.size).contiguous()      # finetune.py:373
     fs.outs = [] if eager else None      # eager: the rasterizer adjoints ride behind their own forward pass (_tail_forward)
     loss, fs.recs, fs.grads, fs.keep = _tail_forward(rt, p_cur, Fl, weight, jobs, streams, eager=fs.outs)
-    fs.streams, fs.states, fs.eff, fs.gcache, fs.svdc, fs.actc = streams, states, eff, gcache, svdc, actc
-    fs.cache_blocks, fs.adj = (cache_blocks if gcache is not None else 0), adj
+    fs.streams, fs.states, fs.eff, fs.call = streams, states, eff, call
     return loss, x, Fl, fs
 
 
@@ -357,8 +324,7 @@ def _frame_backward(rt, fs, g=None):
     from . import _lib as L
     from . import rollout as R
     lib, dev = L.lib(), rt.device
-    sim = rt.sim_fused
-    n, S = rt.n_local, int(sim.substeps)
+    n = rt.n_local
     _, st, _jf, jb, woff, goff, sizes, shapes, gtot, nw = _frame_static(rt)
     # dL/d(x, v, C, F of the last record): B^T of the summed rasterizer adjoints lands in the head of a buffer whose
     # tail (v, C, F: nothing downstream of the roll-out reads them) stays zero
@@ -370,46 +336,27 @@ def _frame_backward(rt, fs, g=None):
     if g is not None:
         dx.mul_(g)
     stream = L.stream_ptr(dev)
-    verified = 0
-    gcache = fs.gcache
-    if gcache is not None and fs.ev is not None:
-        # the record headers travel back right behind the forward sweep: they are here long before the renders are through
-        if R._CACHE_WAIT and not fs.ev.query():
-            fs.ev.synchronize()
-        if fs.ev.query():
-            verified = int(min(fs.status.tolist()) >= 0)
-            rt._status_pool.append((fs.status, fs.ev))
+    call = fs.call
+    ws_bytes = call.ws_bytes
+    ws = rt._scratch("ws", ws_bytes)
+    # (the record headers travel back right behind the forward sweep: they are here long before the renders are through.  The
+    #  workspace still holds this frame's operand-order weights if no other roll-out of the runtime used it in between.  glast
+    #  holds dL/dx and zeros - the loss sees the last record's positions only)
+    cfg = call.backward_cfg(weights_prepared=1 if rt.__dict__.get("_ws_token") == fs.ws_token and ws.data_ptr() == fs.ws_ptr else 0,
+                            last_gF_zero=_LAST_GF_ZERO)
     gfirst = rt._scratch("gfirst", 4 * 24 * n)
     gw = torch.empty(2 * nw, dtype=torch.float32, device=dev)
-    ws_bytes = rt._roll_sizes[1]
-    ws = rt._scratch("ws", ws_bytes)
-    svdc, actc = fs.svdc, fs.actc
-    cfg = L.nm_rollout_cfg(S, float(sim.plasticity.alpha), fs.cache_blocks, verified, fs.adj,
-                           svdc.t.data_ptr() if svdc is not None else None, actc.t.data_ptr() if actc is not None else None,
-                           1 if rt.__dict__.get("_ws_token") == fs.ws_token and ws.data_ptr() == fs.ws_ptr else 0,
-                           _LAST_GF_ZERO)      # (glast holds dL/dx and zeros - the loss sees the last record's positions only)
-    base = fs.eff.data_ptr()
-    w0, w1 = R._WSZ[0], R._WSZ[0] + R._WSZ[1]
-    mle = L.nm_mlp(base, base + 4 * w0, base + 4 * w1)
-    pb = base + 4 * nw
-    mlp = L.nm_mlp(pb, pb + 4 * w0, pb + 4 * w1)
+    mle, mlp = R.mlp_pair(fs.eff.data_ptr(), nw)
     gbase = gw.data_ptr()
     L.check(lib.nm_rollout_backward(rt.model.handle(), n, C.byref(cfg), C.byref(st), C.byref(mle), C.byref(mlp), fs.states.data_ptr(),
-                                    gcache.data_ptr() if gcache is not None else None, glast.data_ptr(), gfirst.data_ptr(), gbase,
-                                    gbase + 4 * nw, ws.data_ptr(), ws_bytes, stream), "nm_rollout_backward")
-    for lease in (svdc, actc):
-        if lease is not None:
-            lease.release()
+                                    call.gcache.data_ptr() if call.gcache is not None else None, glast.data_ptr(), gfirst.data_ptr(),
+                                    gbase, gbase + 4 * nw, ws.data_ptr(), ws_bytes, stream), "nm_rollout_backward")
+    call.close()
     # dL/dW_eff -> dL/dB, dL/dA of the six layers: ONE launch
     gba = torch.empty(gtot, dtype=torch.float32, device=dev)
-    ob = gba.data_ptr()
-    for i in range(6):
-        j = jb[i]
-        j.W = gbase + 4 * woff[i]
-        j.o0 = ob + 4 * goff[i]
-        j.o1 = ob + 4 * (goff[i] + sizes[2 * i])
+    R.lora_grad_jobs(jb, gbase, gba.data_ptr(), woff, goff, sizes)
     L.check(lib.nm_lora_merge_layers_bwd(6, jb, stream), "nm_lora_merge_layers_bwd")
-    fs.recs = fs.grads = fs.keep = fs.states = fs.eff = fs.gcache = fs.svdc = fs.actc = fs.outs = None
+    fs.recs = fs.grads = fs.keep = fs.states = fs.eff = fs.call = fs.outs = None
     return [v.view(sh) for v, sh in zip(gba.split(sizes), shapes)]
 
 
@@ -427,7 +374,7 @@ def _gt_image(rt, img, vi):
 
 class _EpochState(object):
     """What the forward half of a native multi-frame epoch keeps for its reverse sweep."""
-    __slots__ = ("frames", "states", "eff", "n", "S", "adj", "side", "loss_parts", "peak_note")
+    __slots__ = ("calls", "tails", "streams", "states", "eff", "n", "S", "ws_bytes", "side", "loss_parts", "peak_note")
 
 
 def _epoch_forward(rt, gt_frames, weights, views=None, frame_steps=None, start=None, overlap: bool = True):
@@ -461,9 +408,7 @@ def _epoch_forward(rt, gt_frames, weights, views=None, frame_steps=None, start=N
         with torch.no_grad():
             rt.rollout(*start)
     cache_blocks = int(sim.grid_cache_blocks())
-    ws_bytes = int(lib.nm_rollout_workspace(n, S))
-    gc_bytes = int(lib.nm_rollout_gridcache_bytes(S, cache_blocks)) if cache_blocks > 0 else 0
-    svd_bytes, act_bytes = int(lib.nm_rollout_svdcache_bytes(n, S)), int(lib.nm_rollout_actcache_bytes(n, S))
+    ws_bytes, _, svd_bytes, act_bytes = R.rollout_sizes(lib, n, S, cache_blocks)
     ws = rt._scratch("ws", ws_bytes)
     # every frame's pair of caches goes back to the pool after the reverse sweep and is found there by the next epoch (GB-sized
     # buffers: handing them to the caching allocator makes it release and re-acquire device memory inside the training loop);
@@ -472,10 +417,7 @@ def _epoch_forward(rt, gt_frames, weights, views=None, frame_steps=None, start=N
         if nb_ > 0:
             R._POOL_CAPS[(str(dev), int(nb_))] = max(R._POOL_CAPS.get((str(dev), int(nb_)), R._POOL_CAP[0]), nf)
     adj = L.SVD_ADJOINT[sim.svd_adjoint]
-    w0, w1 = R._WSZ[0], R._WSZ[0] + R._WSZ[1]
-    mle = L.nm_mlp(base, base + 4 * w0, base + 4 * w1)
-    pb = base + 4 * nw
-    mlp = L.nm_mlp(pb, pb + 4 * w0, pb + 4 * w1)
+    mle, mlp = R.mlp_pair(base, nw)
     views = list(range(rt.V)) if views is None else list(views)
     jobs = [(vi, None) for vi in views]
     streams = rt._frame_streams(jobs) if len(jobs) > 1 else None
@@ -490,60 +432,43 @@ def _epoch_forward(rt, gt_frames, weights, views=None, frame_steps=None, start=N
     rt._cov6 = rt._cov.detach().float().reshape(-1, 6).contiguous()
     rt._tail_key = None                 # (the single-frame constants are rebuilt by the next frame())
     es = _EpochState()
-    es.frames, es.loss_parts = [], []
+    es.calls, es.tails, es.loss_parts = [], [], []
     cached = recomputed = 0
     rec_bytes = 33 * n * 4
     for f in range(nf):
-        gcache = torch.empty(gc_bytes, dtype=torch.uint8, device=dev) if gc_bytes > 0 else None
-        svdc = R.lease_cache(svd_bytes, dev) if R._SVD_CACHE else None
-        actc = R.lease_cache(act_bytes, dev, force=R._ACT_CACHE == '1') if R._ACT_CACHE != '0' else None
-        cached += actc is not None
-        recomputed += actc is None
-        cfg = L.nm_rollout_cfg(S, float(sim.plasticity.alpha), cache_blocks if gcache is not None else 0, 0, adj,
-                               svdc.t.data_ptr() if svdc is not None else None, actc.t.data_ptr() if actc is not None else None, 0,
-                               _LAST_GF_ZERO if f == nf - 1 else 0)      # (as the reverse sweep of the last frame will: _epoch_backward)
-        sptr = states.data_ptr() + f * S * rec_bytes
-        gptr = gcache.data_ptr() if gcache is not None else None
-        L.check(lib.nm_rollout_forward(rt.model.handle(), n, C.byref(cfg), C.byref(st), C.byref(mle), C.byref(mlp), sptr, gptr,
+        call = R.RolloutCall.open(lib, dev, n, S, sim.plasticity.alpha, adj, cache_blocks,
+                                  last_gF_zero=_LAST_GF_ZERO if f == nf - 1 else 0)      # (as the reverse sweep of the last frame will: _epoch_backward)
+        cached += call.actc is not None
+        recomputed += call.actc is None
+        cfg = call.forward_cfg()
+        L.check(lib.nm_rollout_forward(rt.model.handle(), n, C.byref(cfg), C.byref(st), C.byref(mle), C.byref(mlp),
+                                       states.data_ptr() + f * S * rec_bytes, call.gcache.data_ptr() if call.gcache is not None else None,
                                        ws.data_ptr(), ws_bytes, stream), "nm_rollout_forward")
-        status = ev = None
-        if gcache is not None and R._CACHE_STATUS:
-            status, ev = torch.empty(S, dtype=torch.int32, pin_memory=True), torch.cuda.Event()
-            _status_words_out(rt, lib, gptr, cfg, status, ev, gcache)
-        fr = {"gcache": gcache, "svdc": svdc, "actc": actc, "status": status, "ev": ev, "cache_blocks": cache_blocks if gcache is not None else 0,
-              "tail": None}
-        es.frames.append(fr)
+        call.watch(lib, stream)
+        es.calls.append(call)
+        es.tails.append(None)
         if weights[f] is None:
             continue
         last = states[(f + 1) * S]
         x, Fl = last[:3 * n].view(n, 3), last[15 * n:24 * n].view(n, 9)
         if side is not None:
             side.wait_stream(main)
-        with torch.cuda.stream(side) if side is not None else _NullCtx():
+        with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
             p_cur = x if unit else ((x - rt.center) / rt.size).contiguous()
             rt._de_x_prev, rt._g_prev = de_prev, g_prev
             loss_f, recs, grads, keep = _tail_forward(rt, p_cur, Fl, float(weights[f]), jobs, streams,
                                                       gt={vi: _gt_image(rt, gt_frames[f][i], vi) for i, vi in enumerate(views)},      # (gt_frames[f][i] belongs to views[i])
                                                       step=None if frame_steps is None else frame_steps[f])
             es.loss_parts.append(loss_f)
-            fr["tail"] = (recs, grads, keep, p_cur)
+            es.tails[f] = (recs, grads, keep, p_cur)
             de_prev, g_prev = p_cur, keep[0]          # (detached by construction: nothing here is in a graph)
     if side is not None:
         main.wait_stream(side)
     loss = torch.stack(es.loss_parts).sum() if es.loss_parts else torch.zeros((), dtype=torch.float32, device=dev)
-    es.states, es.eff, es.n, es.S, es.adj, es.side = states, eff, n, S, adj, side
+    es.states, es.eff, es.n, es.S, es.ws_bytes, es.side, es.streams = states, eff, n, S, ws_bytes, side, streams
     es.peak_note = {"frames_with_activation_cache": int(cached), "frames_recomputing": int(recomputed),
                     "activation_cache_budget_GB": round(R.act_cache_budget(dev) / 2 ** 30, 1)}
-    es.frames[0]["streams"] = streams
     return loss, es
-
-
-class _NullCtx(object):
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *a):
-        return False
 
 
 def _epoch_backward(rt, es):
@@ -555,19 +480,14 @@ def _epoch_backward(rt, es):
     from . import _lib as L
     from . import rollout as R
     lib, dev = L.lib(), rt.device
-    n, S, nf = es.n, es.S, len(es.frames)
-    sim = rt.sim_fused
+    n, S, nf = es.n, es.S, len(es.calls)
     _, st, _jf, jb, woff, goff, sizes, shapes, gtot, nw = _frame_static(rt)
     main = torch.cuda.current_stream(dev)
     stream = L.stream_ptr(dev)
     side = es.side
-    streams = es.frames[0].get("streams")
-    base = es.eff.data_ptr()
-    w0, w1 = R._WSZ[0], R._WSZ[0] + R._WSZ[1]
-    mle = L.nm_mlp(base, base + 4 * w0, base + 4 * w1)
-    pb = base + 4 * nw
-    mlp = L.nm_mlp(pb, pb + 4 * w0, pb + 4 * w1)
-    ws_bytes = int(lib.nm_rollout_workspace(n, S))
+    streams = es.streams
+    mle, mlp = R.mlp_pair(es.eff.data_ptr(), nw)
+    ws_bytes = es.ws_bytes
     ws = rt._scratch("ws", ws_bytes)
     bufs = [torch.zeros(24 * n, dtype=torch.float32, device=dev), torch.empty(24 * n, dtype=torch.float32, device=dev)]
     gw_tot = torch.zeros(2 * nw, dtype=torch.float32, device=dev)
@@ -577,26 +497,25 @@ def _epoch_backward(rt, es):
 
     def tail_bwd(f):
         """dL/dx of frame f's renders (None: the frame was excluded), enqueued on the second stream."""
-        fr = es.frames[f]
-        if fr["tail"] is None:
+        if es.tails[f] is None:
             return None
-        recs, grads, keep, _p = fr["tail"]
+        recs, grads, keep, _p = es.tails[f]
         if side is not None:
             side.wait_stream(main)
-        with torch.cuda.stream(side) if side is not None else _NullCtx():
+        with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
             dx = torch.empty(n, 3, dtype=torch.float32, device=dev)
             _tail_backward(rt, recs, grads, streams, dx)
             if not unit:
                 dx.div_(rt.size)
             ev = torch.cuda.Event()
             ev.record()
-        fr["tail"] = None
+        es.tails[f] = None
         return dx, ev
 
     pending = tail_bwd(nf - 1)
     cur = 0
     for f in range(nf - 1, -1, -1):
-        fr = es.frames[f]
+        call = es.calls[f]
         glast, gfirst = bufs[cur], bufs[cur ^ 1]
         nxt = tail_bwd(f - 1) if f > 0 else None        # (runs under this frame's roll-out adjoint)
         if pending is not None:
@@ -604,38 +523,22 @@ def _epoch_backward(rt, es):
             main.wait_event(ev)
             glast[:3 * n].add_(dx.view(-1))
             dx.record_stream(main)
-        verified = 0
-        if fr["gcache"] is not None and fr["ev"] is not None:
-            if R._CACHE_WAIT and not fr["ev"].query():
-                fr["ev"].synchronize()
-            if fr["ev"].query():
-                verified = int(min(fr["status"].tolist()) >= 0)
-        svdc, actc = fr["svdc"], fr["actc"]
-        cfg = L.nm_rollout_cfg(S, float(sim.plasticity.alpha), fr["cache_blocks"], verified, es.adj,
-                               svdc.t.data_ptr() if svdc is not None else None, actc.t.data_ptr() if actc is not None else None, 0,
-                               _LAST_GF_ZERO if f == nf - 1 else 0)     # (the epoch's last frame: nothing flows into its last record but dL/dx)
+        # (the epoch's last frame: nothing flows into its last record but dL/dx)
+        cfg = call.backward_cfg(last_gF_zero=_LAST_GF_ZERO if f == nf - 1 else 0)
         gbase = gw.data_ptr()
         L.check(lib.nm_rollout_backward(rt.model.handle(), n, C.byref(cfg), C.byref(st), C.byref(mle), C.byref(mlp),
                                         es.states.data_ptr() + f * S * rec_bytes,
-                                        fr["gcache"].data_ptr() if fr["gcache"] is not None else None, glast.data_ptr(), gfirst.data_ptr(),
+                                        call.gcache.data_ptr() if call.gcache is not None else None, glast.data_ptr(), gfirst.data_ptr(),
                                         gbase, gbase + 4 * nw, ws.data_ptr(), ws_bytes, stream), "nm_rollout_backward")
-        for lease in (svdc, actc):
-            if lease is not None:
-                lease.release()
-        fr["gcache"] = fr["svdc"] = fr["actc"] = None
+        call.close()
         torch.nan_to_num_(gfirst, 0.0, 0.0, 0.0)       # interface.py:65-74 at the boundary between two frames' roll-outs
         gw_tot.add_(gw)
         pending = nxt
         cur ^= 1
     gba = torch.empty(gtot, dtype=torch.float32, device=dev)
-    ob, gbase = gba.data_ptr(), gw_tot.data_ptr()
-    for i in range(6):
-        j = jb[i]
-        j.W = gbase + 4 * woff[i]
-        j.o0 = ob + 4 * goff[i]
-        j.o1 = ob + 4 * (goff[i] + sizes[2 * i])
+    R.lora_grad_jobs(jb, gw_tot.data_ptr(), gba.data_ptr(), woff, goff, sizes)
     L.check(lib.nm_lora_merge_layers_bwd(6, jb, stream), "nm_lora_merge_layers_bwd")
-    es.frames, es.states = [], None
+    es.calls, es.tails, es.states = [], [], None
     return [v.view(sh) for v, sh in zip(gba.split(sizes), shapes)]
 
 

@@ -132,6 +132,126 @@ class _Lease(object):
         self._forget()
 
 
+_SIZES = {}             # (n, S, cache_blocks) -> bytes of (workspace, grid cache, SVD cache, activation cache): pure functions of the key
+
+
+def rollout_sizes(lib, n: int, S: int, cache_blocks: int):
+    key = (n, S, cache_blocks)
+    sz = _SIZES.get(key)
+    if sz is None:
+        sz = _SIZES[key] = (int(lib.nm_rollout_workspace(n, S)),
+                            int(lib.nm_rollout_gridcache_bytes(S, cache_blocks)) if cache_blocks > 0 else 0,
+                            int(lib.nm_rollout_svdcache_bytes(n, S)), int(lib.nm_rollout_actcache_bytes(n, S)))
+    return sz
+
+
+class RolloutCall(object):
+    """One roll-out call (nm_rollout_forward and its _sharded twin) and what its reverse sweep needs: the grid cache, the leased
+    SVD / activation caches, the record headers on their way to pinned memory, and the ONE set of fields both sweeps' nm_rollout_cfg
+    are built from - the library refuses or silently recomputes when the two disagree.  Shared by the autograd node (_Rollout)
+    and the frame / epoch drivers of harness.py; no autograd, no torch ops but the allocations."""
+    __slots__ = ("S", "alpha", "svd_adjoint", "cache_blocks", "last_gF_zero", "ws_bytes", "gcache", "svdc", "actc", "status",
+                 "event", "landed", "pool")
+
+    @classmethod
+    def open(cls, lib, dev, n, S, alpha, svd_adjoint, cache_blocks, *, want_backward=True, last_gF_zero=0, status_pool=None):
+        """want_backward=False (ground-truth / inference roll-outs): no caches at all.  The SVD cache (U, sigma, V of both nets'
+        inputs per substep, 168 B/particle/substep) and the activation cache (1.2 KB) are leased only while the caches of all
+        live roll-outs together stay inside the budget (act_cache_budget) - a BPTT loop over hundreds of frames falls back to
+        the recompute (the reference's memory profile) instead of running out of memory.  last_gF_zero: what the forward sweep
+        is told and, unless backward_cfg is given another word, the reverse sweep too.  status_pool: a list of (pinned words,
+        event) pairs that watch() takes from and close() hands back to (timed paths); None: a fresh pair per call."""
+        c = cls()
+        cache_blocks = int(cache_blocks) if want_backward else 0
+        c.ws_bytes, gc_bytes, svd_bytes, act_bytes = rollout_sizes(lib, n, S, cache_blocks)
+        c.gcache = torch.empty(gc_bytes, dtype=torch.uint8, device=dev) if gc_bytes > 0 else None
+        c.svdc = lease_cache(svd_bytes, dev) if _SVD_CACHE and want_backward else None
+        c.actc = lease_cache(act_bytes, dev, force=_ACT_CACHE == '1') if _ACT_CACHE != '0' and want_backward else None
+        c.S, c.alpha, c.svd_adjoint, c.last_gF_zero = S, float(alpha), int(svd_adjoint), int(last_gF_zero)
+        c.cache_blocks = cache_blocks if c.gcache is not None else 0
+        c.status = c.event = None
+        c.landed, c.pool = False, status_pool
+        return c
+
+    def _cfg(self, cache_verified, weights_prepared, last_gF_zero):
+        svdc, actc = self.svdc, self.actc
+        return L.nm_rollout_cfg(substeps=self.S, plasticity_alpha=self.alpha, grid_cache_blocks=self.cache_blocks,
+                                cache_verified=cache_verified, svd_adjoint=self.svd_adjoint,
+                                svd_cache=svdc.t.data_ptr() if svdc is not None else None,
+                                act_cache=actc.t.data_ptr() if actc is not None else None,
+                                weights_prepared=weights_prepared, last_gF_zero=last_gF_zero)
+
+    def forward_cfg(self):
+        return self._cfg(0, 0, self.last_gF_zero)
+
+    def backward_cfg(self, *, weights_prepared=0, last_gF_zero=None):
+        """weights_prepared: set by harness._frame_backward alone (the one driver that knows whose weights the workspace holds).
+        last_gF_zero: None = what the forward sweep was told."""
+        return self._cfg(self.verified(), weights_prepared, self.last_gF_zero if last_gF_zero is None else int(last_gF_zero))
+
+    def watch(self, lib, stream):
+        """Asynchronous read-back of the grid cache records' status words into pinned memory behind the forward sweep, an event
+        recorded behind them.  The library writes them from a one-wave kernel straight into the pinned words
+        (nm_rollout_cache_status): the strided device-to-host copy it replaces was a 20 us hole on the frame's stream between the
+        roll-out and the frame's tail."""
+        if self.gcache is None or not _CACHE_STATUS:
+            return
+        pool = self.pool
+        if pool and pool[-1][0].numel() == self.S:
+            self.status, self.event = pool.pop()
+        else:
+            self.status, self.event = torch.empty(self.S, dtype=torch.int32, pin_memory=True), torch.cuda.Event()
+        L.check(lib.nm_rollout_cache_status(self.gcache.data_ptr(), C.byref(self.forward_cfg()), C.c_void_p(self.status.data_ptr()),
+                                            stream), "nm_rollout_cache_status")
+        self.event.record()
+
+    def verified(self) -> int:
+        """nm_rollout_cfg.cache_verified: 1 only when the status words have landed and every record is valid.  The words travel
+        back right behind the forward sweep.  A host that gets here before the device has finished that sweep waits for it (the
+        device still has whatever was enqueued in between - the frame's render - or idles for the few launches it takes to get
+        the reverse sweep going): the unverified sweep it would otherwise run costs four extra launches per substep (+20 us
+        each at 100k particles, 0.4 ms per 20-substep node).  NEUMA_CACHE_WAIT=0: no wait, and words that have not landed are
+        never read - the sweep runs unverified."""
+        ev = self.event
+        if ev is None:
+            return 0
+        if _CACHE_WAIT and not ev.query():
+            ev.synchronize()
+        if not ev.query():
+            return 0
+        self.landed = True
+        return int(min(self.status.tolist()) >= 0)
+
+    def close(self):
+        """After the reverse sweep: both leases back to the pool, the grid cache dropped, the status words handed back (only once
+        they have landed: the device may still write to them otherwise).  A second call does nothing."""
+        for lease in (self.svdc, self.actc):
+            if lease is not None:
+                lease.release()
+        if self.pool is not None and self.landed:
+            self.pool.append((self.status, self.event))
+        self.gcache = self.svdc = self.actc = self.status = self.event = None
+        self.landed = False
+
+
+def mlp_pair(base: int, nw: int):
+    """(nm_mlp of the elasticity net, of the plasticity net) for a packed e0 | e1 | e2 | p0 | p1 | p2 fp32 buffer at `base`, nw
+    floats per net."""
+    w0, w1 = _WSZ[0], _WSZ[0] + _WSZ[1]
+    pb = base + 4 * nw
+    return L.nm_mlp(base, base + 4 * w0, base + 4 * w1), L.nm_mlp(pb, pb + 4 * w0, pb + 4 * w1)
+
+
+def lora_grad_jobs(jb, gw_ptr: int, out_ptr: int, woff, goff, sizes):
+    """Fill the six nm_lora_layer jobs of nm_lora_merge_layers_bwd: dL/dW_eff of layer i at gw_ptr + 4 woff[i], its dL/dB and
+    dL/dA behind one another at out_ptr + 4 goff[i]."""
+    for i in range(6):
+        j = jb[i]
+        j.W = gw_ptr + 4 * woff[i]
+        j.o0 = out_ptr + 4 * goff[i]
+        j.o1 = out_ptr + 4 * (goff[i] + sizes[2 * i])
+
+
 _ZEROS = {}
 
 
@@ -235,29 +355,17 @@ class _Rollout(autograd.Function):
         torch.cat([t.detach().float().reshape(-1) for t in (x, v, C_, F)], out=states[0][:24 * n])
         we = [t.detach().float().contiguous() for t in (e0, e1, e2)]
         wp = [t.detach().float().contiguous() for t in (p0, p1, p2)]
-        ws_bytes = int(lib.nm_rollout_workspace(n, S))
-        ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
         ex = model.exchange
-        # grid cache: only when a backward pass can follow (ground-truth / inference roll-outs skip it)
-        cache_blocks = int(cache_blocks) if any(ctx.needs_input_grad) else 0
-        gc_bytes = int(lib.nm_rollout_gridcache_bytes(S, cache_blocks)) if (cache_blocks > 0 and ex is None) else 0
-        gcache = torch.empty(gc_bytes, dtype=torch.uint8, device=dev) if gc_bytes > 0 else None
-        # SVD cache (U, sigma, V of both nets' inputs per substep, 168 B/particle/substep) and activation cache (1.2 KB): only
-        # when a backward pass can follow, and only while the caches of all live roll-out nodes together stay inside the
-        # budget (act_cache_budget) - a BPTT loop over hundreds of frames falls back to the recompute (the reference's memory
-        # profile) instead of running out of memory
-        svdc = None
-        if _SVD_CACHE and n > 0 and any(ctx.needs_input_grad):
-            svdc = lease_cache(int(lib.nm_rollout_svdcache_bytes(n, S)), dev)
-        actc = None
-        if _ACT_CACHE != '0' and n > 0 and any(ctx.needs_input_grad):
-            actc = lease_cache(int(lib.nm_rollout_actcache_bytes(n, S)), dev, force=_ACT_CACHE == '1')
-        cfg = L.nm_rollout_cfg(S, float(alpha), cache_blocks if gcache is not None else 0, 0, int(svd_adjoint),
-                               L.ptr(svdc.t) if svdc is not None else None, L.ptr(actc.t) if actc is not None else None)
-        ctx.svdc, ctx.actc = svdc, actc
+        # grid cache, SVD and activation caches: only when a backward pass can follow (ground-truth / inference roll-outs skip them);
+        # the sharded sweep sizes its grid cache from the exchange (_forward_sharded)
+        call = RolloutCall.open(lib, dev, n, S, alpha, svd_adjoint, cache_blocks if ex is None else 0,
+                                want_backward=any(ctx.needs_input_grad))
+        ws = torch.empty(max(call.ws_bytes, 4), dtype=torch.uint8, device=dev)
+        ctx.call, ctx.model, ctx.statics, ctx.n = call, model, statics, n
+        ctx.set_materialize_grads(False)      # (backward tells an absent gradient from a zero one: nm_rollout_cfg.last_gF_zero)
         if ex is not None:
-            return _Rollout._forward_sharded(ctx, lib, model, ex, statics, S, float(alpha), int(svd_adjoint), n, states, we, wp, ws,
-                                             ws_bytes, svdc, actc)
+            return _Rollout._forward_sharded(ctx, lib, model, ex, statics, call, n, states, we, wp, ws)
+        cfg = call.forward_cfg()
         st = statics.c_struct()
         mle = L.nm_mlp(*[L.ptr(t) for t in we])
         mlp = L.nm_mlp(*[L.ptr(t) for t in wp])
@@ -265,31 +373,20 @@ class _Rollout(autograd.Function):
             lib.nm_rollout_set_forward_pair(0 if _FWD_PAIR == '0' else 1)
             _FWD_PAIR_SET[0] = True
         L.check(lib.nm_rollout_forward(model.handle(), n, C.byref(cfg), C.byref(st), C.byref(mle), C.byref(mlp), L.ptr(states),
-                                       L.ptr(gcache) if gcache is not None else None, L.ptr(ws), ws_bytes, L.stream_ptr(dev)),
-                "nm_rollout_forward")
-        ctx.model, ctx.statics, ctx.S, ctx.alpha, ctx.n = model, statics, S, float(alpha), n
-        ctx.set_materialize_grads(False)      # (backward tells an absent gradient from a zero one: nm_rollout_cfg.last_gF_zero)
-        ctx.svd_adjoint = int(svd_adjoint)
-        ctx.cache_blocks, ctx.gcache = int(cfg.grid_cache_blocks), gcache
-        ctx.cache_status = ctx.cache_event = None
-        if gcache is not None and _CACHE_STATUS:      # asynchronous read-back of the record headers: by the time the backward pass runs the
-            status = torch.empty(S, dtype=torch.int32, pin_memory=True)       # host usually knows that every record is valid
-            L.check(lib.nm_rollout_cache_status(L.ptr(gcache), C.byref(cfg), C.c_void_p(status.data_ptr()), L.stream_ptr(dev)),
-                    "nm_rollout_cache_status")
-            ev = torch.cuda.Event()
-            ev.record()
-            ctx.cache_status, ctx.cache_event = status, ev
+                                       L.ptr(call.gcache) if call.gcache is not None else None, L.ptr(ws), call.ws_bytes,
+                                       L.stream_ptr(dev)), "nm_rollout_forward")
+        call.watch(lib, L.stream_ptr(dev))      # by the time the backward pass runs the host usually knows that every record is valid
         ctx.save_for_backward(states, *we, *wp)
         last = states[S]
         return (last[:3 * n].view(n, 3), last[3 * n:6 * n].view(n, 3), last[6 * n:15 * n].view(n, 3, 3),
                 last[15 * n:24 * n].view(n, 3, 3))
 
     @staticmethod
-    def _forward_sharded(ctx, lib, model, ex, statics, S, alpha, svd_adjoint, n, states, we, wp, ws, ws_bytes, svdc, actc):
+    def _forward_sharded(ctx, lib, model, ex, statics, call, n, states, we, wp, ws):
         """This rank's share of the particles (model.shard(group)): the library runs the whole S-substep loop, phases and
         collectives, and calls back for the latter (nm_rollout_forward_sharded): one all-gather per roll-out (the frame's
         exchange list is negotiated at the first substep) and one all-reduce per substep and direction."""
-        dev = states.device
+        dev, S = states.device, call.S
         st = statics.c_struct()
         def probe_start_state():
             # one p2g of the inputs with zero stress: the handle then holds the blocks the start state touches
@@ -312,23 +409,18 @@ class _Rollout(autograd.Function):
                 probe_start_state()
             ex.size_frame_lists()
         cap_rec, cap, cap_shared = int(ex.cap), int(ex.cap_dil), int(ex.cap_frame)
-        gcache = torch.empty(int(lib.nm_rollout_gridcache_bytes(S, cap_rec)), dtype=torch.uint8, device=dev)
+        call.gcache = gcache = torch.empty(int(lib.nm_rollout_gridcache_bytes(S, cap_rec)), dtype=torch.uint8, device=dev)
+        call.cache_blocks = cap_rec
         sws_bytes = int(lib.nm_rollout_shard_workspace(ex.world, cap, cap_shared, S))
         sws = torch.empty(sws_bytes, dtype=torch.uint8, device=dev)
         link = _ShardLink(ex, sws)
-        cfg = L.nm_rollout_cfg(S, alpha, cap_rec, 0, svd_adjoint, L.ptr(svdc.t) if svdc is not None else None,
-                               L.ptr(actc.t) if actc is not None else None)
+        cfg = call.forward_cfg()
         mle = L.nm_mlp(*[L.ptr(t) for t in we])
         mlp = L.nm_mlp(*[L.ptr(t) for t in wp])
         link.check(lib.nm_rollout_forward_sharded(model.handle(), n, C.byref(cfg), C.byref(st), C.byref(mle), C.byref(mlp), L.ptr(states),
-                                                  L.ptr(gcache), L.ptr(ws), ws_bytes, C.byref(link.comm), cap, cap_shared, L.ptr(sws),
+                                                  L.ptr(gcache), L.ptr(ws), call.ws_bytes, C.byref(link.comm), cap, cap_shared, L.ptr(sws),
                                                   sws_bytes, L.stream_ptr(dev)), "nm_rollout_forward_sharded")
         ex.watch(lib, sws, dev)          # status word -> pinned host memory; ex.check() raises on a capacity overflow
-        ctx.model, ctx.statics, ctx.S, ctx.alpha, ctx.n = model, statics, S, alpha, n
-        ctx.set_materialize_grads(False)
-        ctx.svd_adjoint = svd_adjoint
-        ctx.cache_blocks, ctx.gcache = cap_rec, gcache
-        ctx.cache_status = ctx.cache_event = None
         ctx.shard = (ex, sws, sws_bytes, cap, cap_shared)
         ctx.save_for_backward(states, *we, *wp)
         last = states[S]
@@ -340,7 +432,8 @@ class _Rollout(autograd.Function):
         lib = L.lib()
         states, e0, e1, e2, p0, p1, p2 = ctx.saved_tensors
         dev = states.device
-        n, S = ctx.n, ctx.S
+        call = ctx.call
+        n, gcache, ws_bytes = ctx.n, call.gcache, call.ws_bytes
         # incoming gradients packed x|v|C|F by one concatenation kernel (absent ones are zeros, kept per size)
         parts = []
         for g, cnt in ((gx, 3 * n), (gv, 3 * n), (gC, 9 * n), (gF, 9 * n)):
@@ -349,23 +442,10 @@ class _Rollout(autograd.Function):
         gfirst = torch.empty(24 * n, dtype=torch.float32, device=dev)
         gwe = torch.empty(sum(_WSZ), dtype=torch.float32, device=dev)
         gwp = torch.empty(sum(_WSZ), dtype=torch.float32, device=dev)
-        ws_bytes = int(lib.nm_rollout_workspace(n, S))
         ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
-        gcache = ctx.gcache
-        verified = 0
-        if gcache is not None and ctx.cache_event is not None:
-            # the record headers travel back right behind the forward sweep.  A host that gets here before the device has
-            # finished that sweep waits for it (the device still has whatever was enqueued in between - the frame's render -
-            # or idles for the few launches it takes to get the reverse sweep going): the unverified sweep it would otherwise
-            # run costs four extra launches per substep (+20 us each at 100k particles, 0.4 ms per 20-substep node)
-            if _CACHE_WAIT and not ctx.cache_event.query():
-                ctx.cache_event.synchronize()
-            verified = int(bool((ctx.cache_status >= 0).all()))
-        svdc, actc = getattr(ctx, "svdc", None), getattr(ctx, "actc", None)
         # (no gradient arrived for F of the last record: the last substep's plasticity adjoint would propagate zeros - the
         #  library leaves that launch out, nm_rollout_cfg.last_gF_zero; the sharded sweep ignores the word)
-        cfg = L.nm_rollout_cfg(S, ctx.alpha, ctx.cache_blocks, verified, ctx.svd_adjoint, L.ptr(svdc.t) if svdc is not None else None,
-                               L.ptr(actc.t) if actc is not None else None, 0, 1 if gF is None else 0)
+        cfg = call.backward_cfg(last_gF_zero=1 if gF is None else 0)
         st = ctx.statics.c_struct()
         mle = L.nm_mlp(L.ptr(e0), L.ptr(e1), L.ptr(e2))
         mlp = L.nm_mlp(L.ptr(p0), L.ptr(p1), L.ptr(p2))
@@ -380,11 +460,7 @@ class _Rollout(autograd.Function):
             L.check(lib.nm_rollout_backward(ctx.model.handle(), n, C.byref(cfg), C.byref(st), C.byref(mle), C.byref(mlp),
                                             L.ptr(states), L.ptr(gcache) if gcache is not None else None, L.ptr(glast), L.ptr(gfirst),
                                             L.ptr(gwe), L.ptr(gwp), L.ptr(ws), ws_bytes, L.stream_ptr(dev)), "nm_rollout_backward")
-        ctx.gcache = None
-        for lease in (svdc, actc):
-            if lease is not None:
-                lease.release()
-        ctx.svdc = ctx.actc = None
+        call.close()
         torch.nan_to_num_(gfirst, 0.0, 0.0, 0.0)   # interface.py:65-74 at the boundary of the fused node
         a, b = _WSZ[0], _WSZ[0] + _WSZ[1]
         return (None, None, None, None, None, None,

@@ -301,6 +301,114 @@ def test_cache_pool_accounting_per_device_trim_and_retry(monkeypatch):
         R.lease_cache(5000, "cpu", force=True)
 
 
+class _StubEvent(object):
+    """query() / synchronize() of torch.cuda.Event; `after_sync`: what query() says once synchronize() has been called."""
+
+    def __init__(self, done, after_sync=True):
+        self.done, self.after_sync, self.syncs = done, after_sync, 0
+
+    def query(self):
+        return self.done
+
+    def synchronize(self):
+        self.syncs += 1
+        self.done = self.after_sync
+
+
+class _StubSizes(object):
+    """The four size queries of the roll-out (any lib object with these serves RolloutCall.open)."""
+    nm_rollout_workspace = staticmethod(lambda n, S: 64 * n)
+    nm_rollout_gridcache_bytes = staticmethod(lambda S, blocks: 16 * S * blocks)
+    nm_rollout_svdcache_bytes = staticmethod(lambda n, S: 168 * n * S)
+    nm_rollout_actcache_bytes = staticmethod(lambda n, S: 1200 * n * S)
+
+
+def test_rollout_call_builds_both_halves_of_the_protocol_from_one_record(monkeypatch):
+    """neuma_amd.rollout.RolloutCall (host logic, CPU tensors): the forward and the reverse nm_rollout_cfg of each of the three
+    drivers (autograd node, lean frame, native epoch) agree on every field the library compares; cache_verified follows ONE rule -
+    1 only when the status words have landed (the event has completed) and none is negative; close() returns both leases and
+    the pooled status words, once."""
+    from neuma_amd import rollout as R
+    monkeypatch.setattr(R, "_BUDGET", {"cpu": 1 << 30})
+    monkeypatch.setattr(R, "_POOL", {})
+    monkeypatch.setattr(R, "_ACT_LIVE", {})
+    monkeypatch.setattr(R, "_SIZES", {})
+    monkeypatch.setattr(R, "_SVD_CACHE", True)
+    monkeypatch.setattr(R, "_ACT_CACHE", "auto")
+    monkeypatch.setattr(R, "_CACHE_WAIT", True)
+    lib, n, S = _StubSizes(), 10, 4
+    shared = ("substeps", "plasticity_alpha", "grid_cache_blocks", "svd_adjoint", "svd_cache", "act_cache")
+    pool = []
+    drivers = {     # name -> (open keywords, backward_cfg keywords, does the driver promise the same last_gF_zero in both halves)
+        "node": (dict(want_backward=True), dict(last_gF_zero=1), False),
+        "node, dL/dF arrives": (dict(want_backward=True), dict(last_gF_zero=0), True),
+        "frame": (dict(last_gF_zero=1, status_pool=pool), dict(weights_prepared=1, last_gF_zero=1), True),
+        "frame, NEUMA_LAST_GF_ZERO=0": (dict(last_gF_zero=0, status_pool=pool), dict(weights_prepared=0, last_gF_zero=0), True),
+        "epoch, last frame": (dict(last_gF_zero=1), dict(last_gF_zero=1), True),
+        "epoch, earlier frame": (dict(last_gF_zero=0), dict(last_gF_zero=0), True),
+        "epoch, word left to the call": (dict(last_gF_zero=1), dict(), True),
+    }
+    for name, (okw, bkw, same_word) in drivers.items():
+        call = R.RolloutCall.open(lib, "cpu", n, S, 1e-3, 1, 7, **okw)
+        assert call.ws_bytes == 64 * n and call.gcache.numel() == 16 * S * 7 and call.svdc is not None and call.actc is not None, name
+        assert R.live_bytes("cpu") == (168 + 1200) * n * S, name
+        fwd = call.forward_cfg()
+        call.status, call.event = torch.zeros(S, dtype=torch.int32), _StubEvent(True)      # (what watch() leaves behind on a GPU)
+        bwd = call.backward_cfg(**bkw)
+        for k in shared:
+            assert getattr(fwd, k) == getattr(bwd, k), (name, k)
+        assert (fwd.substeps, fwd.grid_cache_blocks, fwd.svd_adjoint) == (S, 7, 1) and abs(fwd.plasticity_alpha - 1e-3) < 1e-9, name
+        assert fwd.svd_cache == call.svdc.t.data_ptr() and fwd.act_cache == call.actc.t.data_ptr(), name
+        assert (fwd.cache_verified, fwd.weights_prepared, bwd.cache_verified) == (0, 0, 1), name
+        assert bwd.weights_prepared == bkw.get("weights_prepared", 0), name
+        assert fwd.last_gF_zero == okw.get("last_gF_zero", 0) and bwd.last_gF_zero == bkw.get("last_gF_zero", fwd.last_gF_zero), name
+        assert (fwd.last_gF_zero == bwd.last_gF_zero) or not same_word, name
+        call.close()
+        assert R.live_bytes("cpu") == 0 and sum(len(v) for v in R._POOL.values()) == 2, name
+        assert call.gcache is None and call.svdc is None and call.actc is None and call.status is None and call.event is None, name
+        call.close()                                                      # a second close() is a no-op
+        assert R.live_bytes("cpu") == 0 and sum(len(v) for v in R._POOL.values()) == 2, name
+        assert len(pool) == (1 if "status_pool" in okw else 0), name      # the landed words went back to the pool, once
+        pool.clear()
+    # no backward pass can follow (ground truth, inference): no caches, nothing leased, nothing to verify
+    call = R.RolloutCall.open(lib, "cpu", n, S, 1e-3, 0, 7, want_backward=False)
+    cfg = call.backward_cfg()
+    assert call.gcache is None and (cfg.grid_cache_blocks, cfg.cache_verified, cfg.svd_cache, cfg.act_cache) == (0, 0, None, None)
+    assert R.live_bytes("cpu") == 0
+    # verified(): the words are read only once the event has completed
+    words_ok, words_bad = torch.zeros(S, dtype=torch.int32), torch.tensor([0, 3, -1, 0], dtype=torch.int32)
+    call = R.RolloutCall.open(lib, "cpu", n, S, 1e-3, 0, 7, status_pool=pool)
+    assert call.verified() == 0                                           # nothing was watched
+    call.status, call.event = words_ok, _StubEvent(False)
+    assert call.verified() == 1 and call.event.syncs == 1                 # NEUMA_CACHE_WAIT=1 (default): the host waits for the words
+    call.status, call.event = words_bad, _StubEvent(True)
+    assert call.verified() == 0 and call.backward_cfg().cache_verified == 0      # a negative word: a record is not valid
+    monkeypatch.setattr(R, "_CACHE_WAIT", False)
+    call.landed = False
+    call.status, call.event = words_bad, _StubEvent(False)
+    assert call.verified() == 0 and call.event.syncs == 0 and not call.landed
+    call.status = words_ok                                                # event incomplete: 0 whatever the (unwritten) words say
+    assert call.verified() == 0 and call.backward_cfg().cache_verified == 0 and not call.landed
+    call.close()
+    assert pool == [] and R.live_bytes("cpu") == 0                        # words still in flight are not handed back
+    call = R.RolloutCall.open(lib, "cpu", n, S, 1e-3, 0, 7, status_pool=pool)
+    call.status, call.event = words_ok, _StubEvent(True)
+    assert call.verified() == 1 and call.event.syncs == 0
+    call.close()
+    assert len(pool) == 1 and pool[0][0] is words_ok
+    # the packed weight buffer and the LoRA gradient jobs
+    from neuma_amd import _lib as L
+    nw = sum(R._WSZ)
+    mle, mlp = R.mlp_pair(1000, nw)
+    assert (mle.w0, mle.w1, mle.w2) == (1000, 1000 + 4 * R._WSZ[0], 1000 + 4 * (R._WSZ[0] + R._WSZ[1]))
+    assert (mlp.w0, mlp.w1, mlp.w2) == tuple(p + 4 * nw for p in (mle.w0, mle.w1, mle.w2))
+    jb = (L.nm_lora_layer * 6)()
+    woff, goff, sizes = [0, 10, 30, 60, 100, 150], [0, 5, 12, 21, 32, 45], [2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8]
+    R.lora_grad_jobs(jb, 8000, 16000, woff, goff, sizes)
+    for i in range(6):
+        assert (jb[i].W, jb[i].o0, jb[i].o1) == (8000 + 4 * woff[i], 16000 + 4 * goff[i], 16000 + 4 * (goff[i] + sizes[2 * i]))
+
+
 def test_inference_entry_point_reads_the_reference_demo_configs(golden_dir):
     """`python -m neuma_amd.inference`: its argument parser mirrors experiments/inference.py:48-84 and the loader turns the four
     shipped demo YAMLs into what `inference()` consumes (objects, per-object checkpoints / adaptors / velocities, sim block).
