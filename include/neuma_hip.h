@@ -265,7 +265,9 @@ typedef struct nm_rollout_cfg {
                               * last substep's plasticity adjoint then has nothing to propagate (zero dL/dF, zero weight
                               * gradients) and is not launched.  Given to nm_rollout_forward as well, the last plasticity step
                               * leaves no SVD / activation records (nobody would read them); nm_rollout_backward WITHOUT the flag over
-                              * caches whose forward sweep ran with it fails with NM_ERR_INVALID.  0 = make no assumption. */
+                              * caches whose forward sweep ran with it fails with NM_ERR_INVALID.  The sharded pair ignores the
+                              * word (its forward sweep always writes the records) but keeps the same books: its reverse sweep
+                              * refuses caches last written by such a forward sweep too.  0 = make no assumption. */
 } nm_rollout_cfg;
 #define NM_SVD_ADJOINT_REFERENCE 0
 #define NM_SVD_ADJOINT_POLAR 1

@@ -360,20 +360,15 @@ __device__ __forceinline__ void grid_prologue(const GridPrologue& g, int wg, int
 // ---- internal cross-file entry points of the fused roll-out (nm_rollout.hip)
 int nm_mpm_prologue_forward(nm_mpm* h, GridPrologue* g, bool keep_gv = false);
 int nm_mpm_prologue_backward(nm_mpm* h, const void* gridrec, int cap, GridPrologue* g);
-int nm_mpm_forward_prepared(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur, nm_particles* next, void* gridrec,
-                            int32_t cap_blocks, void* stream);
-int nm_mpm_backward_cached(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur, const nm_particles* next,
-                           const nm_particles* gnext, nm_particles* gcur, const void* gridrec, int32_t cap_blocks, bool verified,
-                           bool prepared, const void* stamp_rec, void* stream);
-// sharded roll-out: the same launches with the exchange of the shared blocks in between (nm_shard.hip / nm_rollout.hip)
+// the reverse substep in two halves; the sharded roll-out exchanges the shared blocks in between (nm_shard.hip / nm_rollout.hip)
 int nm_mpm_backward_cached_begin(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur, const nm_particles* next,
                                  const nm_particles* gnext, nm_particles* gcur, const void* gridrec, int32_t cap_blocks,
                                  bool verified, bool prepared, void* stream);
 int nm_mpm_backward_cached_finish(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur, nm_particles* gcur,
                                   const void* stamp_rec, int32_t cap_blocks, const float* xbuf, void* stream);
+// sharded roll-out, forward: the scatter and the grid update of nm_mpm_forward_prepared_nog2p as two calls around the exchange
 int nm_mpm_forward_prepared_p2g(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur, void* stream);
 int nm_mpm_forward_gridop_x(nm_mpm* h, void* gridrec, int32_t cap_blocks, int32_t* status, const float* xbuf, void* stream);
-int nm_mpm_clear_only(nm_mpm* h, void* stream);
 // pro: grid housekeeping performed in the kernel's prologue (NULL = none)
 int nm_material_bwd_launch(int32_t n, int32_t kind, float alpha, const float* F, const nm_mlp* w, const float* wperm,
                            const float* gout, float* gF, float* wpart, int wmode, const float* trial_C, const int* enabled,

@@ -1405,9 +1405,6 @@ static MpmK scatter_k(const nm_mpm* h, int n) {
 #endif
 static const int kSweepGrid = NM_SWEEP_GRID;  // workgroups for the active-block sweeps (grid-stride over the list)
 
-// clear + p2g + grid_op (shared by forward, backward-recompute and forward_extra).
-// save != null: the forward pass also writes a grid cache record.  restore != null: the reverse sweep restores the
-// grid from the record; p2g / grid_op are still enqueued but return at once unless the record is marked invalid.
 static void mpm_rotate(nm_mpm* h, int& prev, int& now, int& next) {
   prev = h->cur; now = (prev + 1) % 3; next = (prev + 2) % 3;
   h->epoch += 1;
@@ -1415,47 +1412,97 @@ static void mpm_rotate(nm_mpm* h, int& prev, int& now, int& next) {
 }
 
 // the previous substep's list, if the clear left its velocities in place (consumed by the grid update launched next)
-static DroppedBlocks take_dropped(nm_mpm* h, int now) {
-  DroppedBlocks d = {nullptr, nullptr, nullptr, 0};
+static const DroppedBlocks kNoDropped = {nullptr, nullptr, nullptr, 0};
+static DroppedBlocks take_dropped(nm_mpm* h) {
+  DroppedBlocks d = kNoDropped;
   if (h->gv_stale) {
-    const int before = (now + 2) % 3;
+    const int before = (h->cur + 2) % 3;
     d.list = h->list[before]; d.count = h->count + before; d.flags = h->flags; d.epoch = h->epoch;
     h->gv_stale = 0;
   }
   return d;
 }
+static GridRec rec_or_none(const void* gridrec, int cap) {
+  if (gridrec) return gridrec_at(const_cast<void*>(gridrec), cap);
+  return GridRec{nullptr, nullptr, nullptr};
+}
 
+// ---- the one launch site of each substep kernel.  Every entry point below - per-operator, fused roll-out, sharded - is a
+// composition of these; the arguments are what differs between them.  All of them act on the substep h->cur names.
+static int launch_clear(nm_mpm* h, hipStream_t s) {      // opens a substep: rotates the lists, clears what the previous one touched
+  int prev, now, next;
+  mpm_rotate(h, prev, now, next);
+  NM_LAUNCH(k_clear, dim3(NM_CLEAR_WGS), dim3(256), 0, s, h->gm, h->gv, h->gg, h->list[prev], h->count + prev, h->list[now],
+                     h->count + now, h->count + next, h->flags, h->epoch);
+  NM_LAUNCH_CHECK();
+  return NM_OK;
+}
+// skip: header of the record the grid was restored from (the kernel returns at once if that record is valid), or NULL
+static int launch_p2g(nm_mpm* h, int n, const nm_statics* st, const nm_particles* cur, const int* skip, hipStream_t s) {
+  const int now = h->cur;
+  NM_LAUNCH(k_p2g, dim3(scatter_grid(h, n)), dim3(NM_SC_T), 0, s, scatter_k(h, n), n, st->vol, st->rho, st->enabled, cur->x,
+                     cur->v, cur->C, cur->stress, h->gm, h->flags, h->list[now], h->count + now, h->epoch, skip);
+  NM_LAUNCH_CHECK();
+  return NM_OK;
+}
+// save: cache record to write (NULL = none).  xbuf (sharded roll-out): the blocks with an exchange slot come, summed over the
+// ranks, from there.  dropped: take_dropped(h), or kNoDropped to leave h->gv_stale for a later grid update.
+static int launch_grid_op(nm_mpm* h, void* save, int cap, const int* skip, int32_t* status, const float* xbuf,
+                          const DroppedBlocks& dropped, hipStream_t s) {
+  const int now = h->cur;
+  NM_LAUNCH(k_grid_op, dim3(kSweepGrid), dim3(256), 0, s, h->k, h->gm, h->gv, h->list[now], h->count + now, rec_or_none(save, cap),
+                     cap, skip, (int*)status, (const int*)(xbuf ? h->sh_slot : nullptr), (const float4*)xbuf, dropped);
+  NM_LAUNCH_CHECK();
+  return NM_OK;
+}
+static int launch_g2p(nm_mpm* h, int n, const nm_statics* st, const nm_particles* cur, nm_particles* next, hipStream_t s) {
+  NM_LAUNCH(k_g2p, dim3(nm_div_up(n, 256)), dim3(256), 0, s, h->k, n, st->clip_bound, st->enabled, cur->x, cur->v, cur->C,
+                     cur->F, h->gv, next->x, next->v, next->C, next->F, h->fresh_rows);
+  NM_LAUNCH_CHECK();
+  return NM_OK;
+}
+static int launch_g2p_bwd(nm_mpm* h, int n, const nm_statics* st, const nm_particles* cur, const nm_particles* next,
+                          const nm_particles* gnext, nm_particles* gcur, hipStream_t s) {
+  NM_LAUNCH(k_g2p_bwd, dim3(scatter_grid(h, n)), dim3(NM_SC_T), 0, s, scatter_k(h, n), n, st->clip_bound, st->enabled, cur->x, cur->F,
+                     next->v, next->C, gnext->x, gnext->v, gnext->C, gnext->F, h->gv, h->gg, gcur->x, gcur->F);
+  NM_LAUNCH_CHECK();
+  return NM_OK;
+}
+// stamp_rec: record of the substep the sweep visits next; its blocks get flagged with stamp_epoch for that substep's prologue
+static int launch_grid_op_bwd(nm_mpm* h, const void* stamp_rec, int cap, int stamp_epoch, const float* xbuf, hipStream_t s) {
+  const int now = h->cur;
+  NM_LAUNCH(k_grid_op_bwd, dim3(kSweepGrid), dim3(256), 0, s, (const int*)h->list[now], (const int*)(h->count + now), (const float4*)h->gm,
+                     h->gg, h->flags, (const int*)(xbuf ? h->sh_slot : nullptr), (const float4*)xbuf, h->k, rec_or_none(stamp_rec, cap),
+                     stamp_epoch);
+  NM_LAUNCH_CHECK();
+  return NM_OK;
+}
+static int launch_p2g_bwd(nm_mpm* h, int n, const nm_statics* st, const nm_particles* cur, nm_particles* gcur, hipStream_t s) {
+  NM_LAUNCH(k_p2g_bwd, dim3(nm_div_up(n, 256)), dim3(256), 0, s, h->k, n, st->vol, st->rho, st->enabled, cur->x, cur->v, cur->C,
+                     cur->stress, h->gg, gcur->x, gcur->v, gcur->C, gcur->stress);
+  NM_LAUNCH_CHECK();
+  return NM_OK;
+}
+
+// clear + p2g + grid_op (shared by forward, backward-recompute and forward_extra).
+// save != null: the forward pass also writes a grid cache record.  restore != null: the reverse sweep restores the
+// grid from the record; p2g / grid_op are still enqueued but return at once unless the record is marked invalid.
+// precleared: a GridPrologue (nm_mpm_prologue_forward) has rotated the lists and cleared the grid already.
 static int mpm_build_grid(nm_mpm* h, int n, const nm_statics* st, const nm_particles* cur, hipStream_t s, void* save = nullptr,
                           const void* restore = nullptr, int cap = 0, bool restore_verified = false, bool precleared = false) {
-  int prev, now, next;
-  if (precleared) {   // a GridPrologue (nm_mpm_prologue_forward) has rotated the lists and cleared the grid already
-    now = h->cur;
-  } else {
-    mpm_rotate(h, prev, now, next);
-    NM_LAUNCH(k_clear, dim3(NM_CLEAR_WGS), dim3(256), 0, s, h->gm, h->gv, h->gg, h->list[prev], h->count + prev, h->list[now],
-                       h->count + now, h->count + next, h->flags, h->epoch);
-    NM_LAUNCH_CHECK();
-  }
-  GridRec none = {nullptr, nullptr, nullptr};
-  GridRec srec = save ? gridrec_at(save, cap) : none;
+  int rc = precleared ? NM_OK : launch_clear(h, s);
+  if (rc) return rc;
   const int* skip = nullptr;
   if (restore) {
     GridRec rrec = gridrec_at(const_cast<void*>(restore), cap);
-    NM_LAUNCH(k_grid_restore, dim3(kSweepGrid), dim3(256), 0, s, h->k, rrec, h->gm, h->gv, h->list[now], h->count + now);
+    NM_LAUNCH(k_grid_restore, dim3(kSweepGrid), dim3(256), 0, s, h->k, rrec, h->gm, h->gv, h->list[h->cur], h->count + h->cur);
     NM_LAUNCH_CHECK();
     skip = rrec.hdr;
     if (restore_verified) return NM_OK;   // the host has seen this record's header: it is valid, nothing to fall back to
   }
-  if (n > 0) {
-    NM_LAUNCH(k_p2g, dim3(scatter_grid(h, n)), dim3(NM_SC_T), 0, s, scatter_k(h, n), n, st->vol, st->rho, st->enabled, cur->x,
-                       cur->v, cur->C, cur->stress, h->gm, h->flags, h->list[now], h->count + now, h->epoch, skip);
-    NM_LAUNCH_CHECK();
-  }
-  const DroppedBlocks dropped = take_dropped(h, now);
-  NM_LAUNCH(k_grid_op, dim3(kSweepGrid), dim3(256), 0, s, h->k, h->gm, h->gv, h->list[now], h->count + now, srec, cap, skip,
-            (int*)nullptr, (const int*)nullptr, (const float4*)nullptr, dropped);
-  NM_LAUNCH_CHECK();
-  return NM_OK;
+  if (n > 0) rc = launch_p2g(h, n, st, cur, skip, s);
+  if (rc) return rc;
+  return launch_grid_op(h, save, cap, skip, nullptr, nullptr, take_dropped(h), s);
 }
 
 // ---- roll-out only: the clear / restore of a substep rides in the prologue of the constitutive kernel in front of it
@@ -1489,6 +1536,27 @@ static int check_particles(const nm_statics* st, const nm_particles* p, bool nee
   if (need_stress) NM_REQUIRE(p->stress, "null stress");
   return NM_OK;
 }
+static int check_next_state(const nm_particles* next) {
+  NM_REQUIRE(next && next->v && next->C, "next state (v, C) required");
+  return NM_OK;
+}
+static int check_grad_in(const nm_particles* gnext) {
+  NM_REQUIRE(gnext && gnext->x && gnext->v && gnext->C && gnext->F, "null incoming gradients");
+  return NM_OK;
+}
+static int check_grad_out(const nm_particles* gcur) {
+  NM_REQUIRE(gcur && gcur->x && gcur->v && gcur->C && gcur->F && gcur->stress, "null outgoing gradients");
+  return NM_OK;
+}
+// what the g2p adjoint reads and writes
+static int check_g2p_bwd(const nm_statics* st, const nm_particles* cur, const nm_particles* next, const nm_particles* gnext,
+                         const nm_particles* gcur) {
+  int rc = check_particles(st, cur, true);
+  if (!rc) rc = check_next_state(next);
+  if (!rc) rc = check_grad_in(gnext);
+  if (!rc) rc = check_grad_out(gcur);
+  return rc;
+}
 
 extern "C" int nm_mpm_forward(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur, nm_particles* next,
                               void* stream) {
@@ -1512,10 +1580,7 @@ static int mpm_forward_impl(nm_mpm* h, int32_t n, const nm_statics* st, const nm
   if (rc) return rc;
   h->resident_rec = gridrec; h->resident_epoch = h->epoch;
   if (!next) return NM_OK;   // g2p is performed by the caller's next kernel (nm_mpm_g2p_fuse)
-  NM_LAUNCH(k_g2p, dim3(nm_div_up(n, 256)), dim3(256), 0, s, h->k, n, st->clip_bound, st->enabled, cur->x,
-                     cur->v, cur->C, cur->F, h->gv, next->x, next->v, next->C, next->F, h->fresh_rows);
-  NM_LAUNCH_CHECK();
-  return NM_OK;
+  return launch_g2p(h, n, st, cur, next, s);
 }
 
 extern "C" int nm_mpm_forward_ex(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur, nm_particles* next,
@@ -1523,12 +1588,8 @@ extern "C" int nm_mpm_forward_ex(nm_mpm* h, int32_t n, const nm_statics* st, con
   return mpm_forward_impl(h, n, st, cur, next, gridrec, cap_blocks, false, stream);
 }
 
-// roll-out: the grid was cleared by a GridPrologue (nm_mpm_prologue_forward) in the kernel launched just before
-int nm_mpm_forward_prepared(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur, nm_particles* next, void* gridrec,
-                            int32_t cap_blocks, void* stream) {
-  return mpm_forward_impl(h, n, st, cur, next, gridrec, cap_blocks, true, stream);
-}
-
+// roll-out: the grid was cleared by a GridPrologue (nm_mpm_prologue_forward) in the kernel launched just before, and the
+// g2p runs inside the one launched next
 int nm_mpm_forward_prepared_nog2p(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur, void* gridrec,
                                   int32_t cap_blocks, void* stream) {
   return mpm_forward_impl(h, n, st, cur, nullptr, gridrec, cap_blocks, true, stream);
@@ -1569,12 +1630,7 @@ extern "C" int nm_mpm_backward(nm_mpm* h, int32_t n, const nm_statics* st, const
   return nm_mpm_backward_ex(h, n, st, cur, next, gnext, gcur, nullptr, 0, stream);
 }
 
-extern "C" int nm_mpm_backward_ex(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur,
-                                  const nm_particles* next, const nm_particles* gnext, nm_particles* gcur,
-                                  const void* gridrec, int32_t cap_blocks, void* stream) {
-  return nm_mpm_backward_cached(h, n, st, cur, next, gnext, gcur, gridrec, cap_blocks, false, false, nullptr, stream);
-}
-
+// The reverse substep in two halves (the sharded roll-out sums the exchange blocks between them).
 // verified: the host has seen the record's header (valid) - no fall-back launches.  prepared: a GridPrologue
 // (nm_mpm_prologue_backward) restored the grid in the kernel launched just before.  stamp_rec: record of the substep the
 // sweep visits next; its blocks get flagged for that substep's prologue.
@@ -1589,11 +1645,8 @@ int nm_mpm_backward_cached_begin(nm_mpm* h, int32_t n, const nm_statics* st, con
     if (!prepared) return mpm_build_grid(h, 0, st, cur, s, nullptr, gridrec, cap_blocks, verified && gridrec != nullptr);
     return NM_OK;
   }
-  int rc = check_particles(st, cur, true);
+  int rc = check_g2p_bwd(st, cur, next, gnext, gcur);
   if (rc) return rc;
-  NM_REQUIRE(next && next->v && next->C, "next state (v, C) required");
-  NM_REQUIRE(gnext && gnext->x && gnext->v && gnext->C && gnext->F, "null incoming gradients");
-  NM_REQUIRE(gcur && gcur->x && gcur->v && gcur->C && gcur->F && gcur->stress, "null outgoing gradients");
   // The reverse sweep usually starts right behind the forward one: the grid still holds the last substep - {mv, m}, velocities,
   // active list, a clean adjoint array (nothing but a reverse substep writes it, and each one cleans up behind the previous) -
   // exactly what clear + restore would rebuild from the (valid) record.  Two launches less per roll-out; for the one-substep
@@ -1604,35 +1657,24 @@ int nm_mpm_backward_cached_begin(nm_mpm* h, int32_t n, const nm_statics* st, con
     if (rc) return rc;
   }
   h->resident_rec = nullptr;      // (the adjoint scatter below dirties the grid's adjoint array: resident no more)
-  NM_LAUNCH(k_g2p_bwd, dim3(scatter_grid(h, n)), dim3(NM_SC_T), 0, s, scatter_k(h, n), n, st->clip_bound, st->enabled, cur->x, cur->F, next->v,
-                     next->C, gnext->x, gnext->v, gnext->C, gnext->F, h->gv, h->gg, gcur->x, gcur->F);
-  NM_LAUNCH_CHECK();
-  return NM_OK;
+  return launch_g2p_bwd(h, n, st, cur, next, gnext, gcur, s);
 }
 // xbuf != NULL (sharded roll-out): the node-velocity adjoint of the blocks with an exchange slot comes, summed over the
 // ranks, from there
 int nm_mpm_backward_cached_finish(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur, nm_particles* gcur,
                                   const void* stamp_rec, int32_t cap_blocks, const float* xbuf, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  const int now = h->cur;
-  GridRec stamp = {nullptr, nullptr, nullptr};
-  if (stamp_rec) stamp = gridrec_at(const_cast<void*>(stamp_rec), cap_blocks);
-  NM_LAUNCH(k_grid_op_bwd, dim3(kSweepGrid), dim3(256), 0, s, (const int*)h->list[now], (const int*)(h->count + now), (const float4*)h->gm, h->gg,
-                     h->flags, (const int*)(xbuf ? h->sh_slot : nullptr), (const float4*)xbuf, h->k, stamp, h->epoch + 1);
-  NM_LAUNCH_CHECK();
-  if (n == 0) return NM_OK;
-  NM_LAUNCH(k_p2g_bwd, dim3(nm_div_up(n, 256)), dim3(256), 0, s, h->k, n, st->vol, st->rho, st->enabled, cur->x, cur->v, cur->C,
-                     cur->stress, h->gg, gcur->x, gcur->v, gcur->C, gcur->stress);
-  NM_LAUNCH_CHECK();
-  return NM_OK;
+  int rc = launch_grid_op_bwd(h, stamp_rec, cap_blocks, h->epoch + 1, xbuf, s);
+  if (rc || n == 0) return rc;
+  return launch_p2g_bwd(h, n, st, cur, gcur, s);
 }
-int nm_mpm_backward_cached(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur, const nm_particles* next,
-                           const nm_particles* gnext, nm_particles* gcur, const void* gridrec, int32_t cap_blocks, bool verified,
-                           bool prepared, const void* stamp_rec, void* stream) {
+extern "C" int nm_mpm_backward_ex(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur,
+                                  const nm_particles* next, const nm_particles* gnext, nm_particles* gcur,
+                                  const void* gridrec, int32_t cap_blocks, void* stream) {
   if (n == 0) return NM_OK;
-  int rc = nm_mpm_backward_cached_begin(h, n, st, cur, next, gnext, gcur, gridrec, cap_blocks, verified, prepared, stream);
+  int rc = nm_mpm_backward_cached_begin(h, n, st, cur, next, gnext, gcur, gridrec, cap_blocks, false, false, stream);
   if (rc) return rc;
-  return nm_mpm_backward_cached_finish(h, n, st, cur, gcur, stamp_rec, cap_blocks, nullptr, stream);
+  return nm_mpm_backward_cached_finish(h, n, st, cur, gcur, nullptr, cap_blocks, nullptr, stream);
 }
 
 // sharded roll-out, forward: this rank's scatter alone (the grid was cleared by a GridPrologue), then - after the exchange -
@@ -1641,31 +1683,11 @@ int nm_mpm_forward_prepared_p2g(nm_mpm* h, int32_t n, const nm_statics* st, cons
   if (n == 0) return NM_OK;
   int rc = check_particles(st, cur, true);
   if (rc) return rc;
-  const int now = h->cur;
-  NM_LAUNCH(k_p2g, dim3(scatter_grid(h, n)), dim3(NM_SC_T), 0, (hipStream_t)stream, scatter_k(h, n), n, st->vol, st->rho, st->enabled, cur->x,
-                     cur->v, cur->C, cur->stress, h->gm, h->flags, h->list[now], h->count + now, h->epoch, (const int*)nullptr);
-  NM_LAUNCH_CHECK();
-  return NM_OK;
+  return launch_p2g(h, n, st, cur, nullptr, (hipStream_t)stream);
 }
 int nm_mpm_forward_gridop_x(nm_mpm* h, void* gridrec, int32_t cap_blocks, int32_t* status, const float* xbuf, void* stream) {
   NM_REQUIRE(!gridrec || cap_blocks > 0, "grid cache record without capacity");
-  const int now = h->cur;
-  GridRec none = {nullptr, nullptr, nullptr};
-  const DroppedBlocks dropped = take_dropped(h, now);
-  NM_LAUNCH(k_grid_op, dim3(kSweepGrid), dim3(256), 0, (hipStream_t)stream, h->k, h->gm, h->gv, h->list[now], h->count + now,
-                     gridrec ? gridrec_at(gridrec, cap_blocks) : none, cap_blocks, (const int*)nullptr, (int*)status,
-                     (const int*)(xbuf ? h->sh_slot : nullptr), (const float4*)xbuf, dropped);
-  NM_LAUNCH_CHECK();
-  return NM_OK;
-}
-// clear + rotate for a rank without particles (no constitutive kernel carries the prologue there)
-int nm_mpm_clear_only(nm_mpm* h, void* stream) {
-  int prev, now, next;
-  mpm_rotate(h, prev, now, next);
-  NM_LAUNCH(k_clear, dim3(NM_CLEAR_WGS), dim3(256), 0, (hipStream_t)stream, h->gm, h->gv, h->gg, h->list[prev], h->count + prev,
-                     h->list[now], h->count + now, h->count + next, h->flags, h->epoch);
-  NM_LAUNCH_CHECK();
-  return NM_OK;
+  return launch_grid_op(h, gridrec, cap_blocks, nullptr, status, xbuf, take_dropped(h), (hipStream_t)stream);
 }
 
 __global__ void k_fill_int(int* __restrict__ a, int n, int v) {
@@ -1727,18 +1749,9 @@ extern "C" int nm_mpm_p2g(nm_mpm* h, int32_t n, const nm_statics* st, const nm_p
     if (rc) return rc;
   }
   hipStream_t s = (hipStream_t)stream;
-  const int prev = h->cur, now = (prev + 1) % 3, next = (prev + 2) % 3;
-  h->epoch += 1;
-  NM_LAUNCH(k_clear, dim3(NM_CLEAR_WGS), dim3(256), 0, s, h->gm, h->gv, h->gg, h->list[prev], h->count + prev, h->list[now],
-                     h->count + now, h->count + next, h->flags, h->epoch);
-  NM_LAUNCH_CHECK();
-  if (n > 0) {   // a rank without particles still takes part in the exchange with an empty list
-    NM_LAUNCH(k_p2g, dim3(scatter_grid(h, n)), dim3(NM_SC_T), 0, s, scatter_k(h, n), n, st->vol, st->rho, st->enabled, cur->x,
-                       cur->v, cur->C, cur->stress, h->gm, h->flags, h->list[now], h->count + now, h->epoch, (const int*)nullptr);
-    NM_LAUNCH_CHECK();
-  }
-  h->cur = now;
-  return NM_OK;
+  int rc = launch_clear(h, s);
+  if (rc || n == 0) return rc;   // a rank without particles still takes part in the exchange with an empty list
+  return launch_p2g(h, n, st, cur, nullptr, s);
 }
 
 extern "C" int nm_mpm_forward_finish(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur, nm_particles* next,
@@ -1747,21 +1760,13 @@ extern "C" int nm_mpm_forward_finish(nm_mpm* h, int32_t n, const nm_statics* st,
   NM_REQUIRE(!gridrec || cap_blocks > 0, "grid cache record without capacity");
   NM_REQUIRE(n >= 0, "negative particle count");
   hipStream_t s = (hipStream_t)stream;
-  const int now = h->cur;
-  GridRec none = {nullptr, nullptr, nullptr};
-  NM_LAUNCH(k_grid_op, dim3(kSweepGrid), dim3(256), 0, s, h->k, h->gm, h->gv, h->list[now], h->count + now,
-                     gridrec ? gridrec_at(gridrec, cap_blocks) : none, cap_blocks, (const int*)nullptr, (int*)status,
-                     (const int*)nullptr, (const float4*)nullptr, DroppedBlocks{nullptr, nullptr, nullptr, 0});
-  NM_LAUNCH_CHECK();
-  if (n == 0) return NM_OK;
-  int rc = check_particles(st, cur, true);
+  int rc = launch_grid_op(h, gridrec, cap_blocks, nullptr, status, nullptr, kNoDropped, s);
+  if (rc || n == 0) return rc;
+  rc = check_particles(st, cur, true);
   if (rc) return rc;
   rc = check_particles(st, next, false);
   if (rc) return rc;
-  NM_LAUNCH(k_g2p, dim3(nm_div_up(n, 256)), dim3(256), 0, s, h->k, n, st->clip_bound, st->enabled, cur->x, cur->v, cur->C,
-                     cur->F, h->gv, next->x, next->v, next->C, next->F, h->fresh_rows);
-  NM_LAUNCH_CHECK();
-  return NM_OK;
+  return launch_g2p(h, n, st, cur, next, s);
 }
 
 extern "C" int nm_mpm_backward_begin(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur, const nm_particles* next,
@@ -1775,15 +1780,9 @@ extern "C" int nm_mpm_backward_begin(nm_mpm* h, int32_t n, const nm_statics* st,
   int rc = mpm_build_grid(h, 0, st, cur, s, nullptr, gridrec, cap_blocks, true);
   if (rc) return rc;
   if (n == 0) return NM_OK;
-  rc = check_particles(st, cur, true);
+  rc = check_g2p_bwd(st, cur, next, gnext, gcur);
   if (rc) return rc;
-  NM_REQUIRE(next && next->v && next->C, "next state (v, C) required");
-  NM_REQUIRE(gnext && gnext->x && gnext->v && gnext->C && gnext->F, "null incoming gradients");
-  NM_REQUIRE(gcur && gcur->x && gcur->v && gcur->C && gcur->F && gcur->stress, "null outgoing gradients");
-  NM_LAUNCH(k_g2p_bwd, dim3(scatter_grid(h, n)), dim3(NM_SC_T), 0, s, scatter_k(h, n), n, st->clip_bound, st->enabled, cur->x, cur->F,
-                     next->v, next->C, gnext->x, gnext->v, gnext->C, gnext->F, h->gv, h->gg, gcur->x, gcur->F);
-  NM_LAUNCH_CHECK();
-  return NM_OK;
+  return launch_g2p_bwd(h, n, st, cur, next, gnext, gcur, s);
 }
 
 extern "C" int nm_mpm_backward_finish(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur, nm_particles* gcur,
@@ -1791,19 +1790,12 @@ extern "C" int nm_mpm_backward_finish(nm_mpm* h, int32_t n, const nm_statics* st
   NM_REQUIRE(h, "null handle");
   NM_REQUIRE(n >= 0, "negative particle count");
   hipStream_t s = (hipStream_t)stream;
-  const int now = h->cur;
-  GridRec nostamp = {nullptr, nullptr, nullptr};
-  NM_LAUNCH(k_grid_op_bwd, dim3(kSweepGrid), dim3(256), 0, s, (const int*)h->list[now], (const int*)(h->count + now), (const float4*)h->gm, h->gg,
-                     h->flags, (const int*)nullptr, (const float4*)nullptr, h->k, nostamp, 0);
-  NM_LAUNCH_CHECK();
-  if (n == 0) return NM_OK;
-  int rc = check_particles(st, cur, true);
+  int rc = launch_grid_op_bwd(h, nullptr, 0, 0, nullptr, s);
+  if (rc || n == 0) return rc;
+  rc = check_particles(st, cur, true);
+  if (!rc) rc = check_grad_out(gcur);
   if (rc) return rc;
-  NM_REQUIRE(gcur && gcur->x && gcur->v && gcur->C && gcur->F && gcur->stress, "null outgoing gradients");
-  NM_LAUNCH(k_p2g_bwd, dim3(nm_div_up(n, 256)), dim3(256), 0, s, h->k, n, st->vol, st->rho, st->enabled, cur->x, cur->v, cur->C,
-                     cur->stress, h->gg, gcur->x, gcur->v, gcur->C, gcur->stress);
-  NM_LAUNCH_CHECK();
-  return NM_OK;
+  return launch_p2g_bwd(h, n, st, cur, gcur, s);
 }
 
 extern "C" int nm_mpm_grid_stats(nm_mpm* h, int32_t* active_blocks, int32_t* nodes_with_mass, void* stream) {
