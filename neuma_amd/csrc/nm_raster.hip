@@ -479,6 +479,13 @@ __global__ void __launch_bounds__(256) k_preprocess(RK k, int K, const float* __
 }
 
 // depth slab of a view-space depth: monotone in z
+// inclusive prefix sum of x over the 64 lanes of a wave
+__device__ __forceinline__ int wave_incl_scan(int x) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o, 64); if (lane >= o) x += y; }
+  return x;
+}
 __device__ __forceinline__ int slab_of(float z, uint32_t zmin_bits, uint32_t zmax_bits) {
   const float zmin = __uint_as_float(zmin_bits), zmax = __uint_as_float(zmax_bits);
   const float span = zmax - zmin;
@@ -543,9 +550,7 @@ __global__ void __launch_bounds__(256) k_bin_count(RK k, int K, int nbx, const i
   //      entry), exclusive prefix over the lanes, ONE atomic for the wave
   const int nbw = bx1 - bx0 + 1;
   const int mine = live ? nbw * (by1 - by0 + 1) : 0;
-  int incl = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(incl, o, 64); if (lane >= o) incl += y; }
+  const int incl = wave_incl_scan(mine);
   const int wave_total = __shfl(incl, 63, 64);
   BC_T(1)
   // ONE reservation per workgroup: every returning atomic on this one word queues behind all the others (~12 ns each;
@@ -1044,9 +1049,7 @@ __global__ void __launch_bounds__(256) k_bin_count2(RK k, int nbx, int nbin, con
   const int bx0 = x0 / NM_BT, bx1 = live ? (x1 - 1) / NM_BT : -1, by0 = y0 / NM_BT, by1 = live ? (y1 - 1) / NM_BT : -1;
   const int nbw = bx1 - bx0 + 1;
   const int mine = live ? nbw * (by1 - by0 + 1) : 0;
-  int incl = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(incl, o, 64); if (lane >= o) incl += y; }
+  const int incl = wave_incl_scan(mine);
   const int wave_total = __shfl(incl, 63, 64);
   s_excl[wv][lane] = incl - mine;
   s_tc[wv][lane] = tc;
@@ -1270,9 +1273,7 @@ __device__ __forceinline__ uint32_t composite_range(CompLds& L, long long lo, lo
       m16 |= (b4 & ok) << (4 * v4);
     }
     const int mine = __popc(m16);
-    int incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(incl, o, 64); if (lane >= o) incl += y; }
+    const int incl = wave_incl_scan(mine);
     if (lane == 63) L.wcnt[wave] = incl;
     __syncthreads();
     int before = 0, nh = 0;
@@ -1369,6 +1370,23 @@ __device__ __forceinline__ uint32_t composite_range(CompLds& L, long long lo, lo
   p.done = !(fx < kInf);
   return reached;
 }
+// What a workgroup's thread knows of its tile: its (first) pixel - a lane owns PX pixels below one another -, the tile's bin, its
+// bit in the bin's tile masks and where the bin's list starts.  The list ends at list_end() (a render that overflowed: nowhere)
+struct TileAt { int px, py; bool inside; int bin; uint32_t bit; long long lo; };
+template <int PX = 1>
+__device__ __forceinline__ TileAt tile_at(const RK& k, int nbx, int tile_x, int tile_y, const uint32_t* __restrict__ off) {
+  const int tid = threadIdx.x;
+  TileAt t;
+  t.px = tile_x * NM_TILE + (tid & 15); t.py = tile_y * NM_TILE + PX * (tid >> 4);
+  t.inside = t.px < k.W && t.py < k.H;
+  t.bin = (tile_y / NM_BT) * nbx + tile_x / NM_BT;
+  t.bit = 1u << ((tile_y % NM_BT) * NM_BT + tile_x % NM_BT);
+  t.lo = off[t.bin * NM_NS];
+  return t;
+}
+__device__ __forceinline__ long long list_end(const uint32_t* __restrict__ off, int bin, long long cap) {
+  return min((long long)off[(bin + 1) * NM_NS], cap);
+}
 __device__ __forceinline__ void write_pixel(const RK& k, int px, int py, const Pix& p, float* __restrict__ final_T,
                                             uint32_t* __restrict__ n_contrib, float* __restrict__ out) {
   size_t pix = (size_t)py * k.W + px, hw = (size_t)k.H * k.W;
@@ -1387,13 +1405,9 @@ __device__ __forceinline__ void render_whole(CompLds& L, const RK& k, int nbx, i
                                              uint32_t* __restrict__ hint) {
   if (tile_rec[tile_y * k.gx + tile_x] != 0xFFFFFFFFu) return;      // a candidate of the split compositing (render_seg)
   const int tid = threadIdx.x;
-  const int px = tile_x * NM_TILE + (tid & 15), py = tile_y * NM_TILE + (tid >> 4);
-  const bool inside = px < k.W && py < k.H;
-  const int bin = (tile_y / NM_BT) * nbx + tile_x / NM_BT;
-  const uint32_t bit = 1u << ((tile_y % NM_BT) * NM_BT + tile_x % NM_BT);
-  const long long lo = off[bin * NM_NS];
+  const auto [px, py, inside, bin, bit, lo] = tile_at(k, nbx, tile_x, tile_y, off);
   // capacity overflow (hdr[3]): slots of the lists were never written - render the background only, the caller re-runs
-  const long long hi = hdr[3] ? lo : min((long long)off[(bin + 1) * NM_NS], cap);
+  const long long hi = hdr[3] ? lo : list_end(off, bin, cap);
   Pix p = {1.f, 0.f, 0.f, 0.f, 0u, !inside};
   const uint32_t reached = composite_range(L, lo, lo, hi, bit, keys, vals, recs, (uint32_t)k.K * (uint32_t)sizeof(GRec), (float)px, (float)py, p);
   if (inside) write_pixel(k, px, py, p, final_T, n_contrib, out);
@@ -1416,7 +1430,7 @@ __device__ __forceinline__ void render_whole(CompLds& L, const RK& k, int nbx, i
 //                     it, or stops inside it - then the segment is walked again for those pixels from the true T, so the
 //                     reference's termination rule (stop when T would fall below 1e-4, forward.cu) is kept exactly;
 //                     the tile's last workgroup to finish sums the records.
-// The reverse sweep walks the segments of a split tile in parallel too (k_render_bwd_seg).
+// The reverse sweep walks the segments of a split tile in parallel too (render_bwd_tile).
 // The render's status words for the host, as three 64-bit values behind one another (one 24-byte copy instead of three
 // 4-byte ones - each was a blit kernel of its own): pairs binned | overflow flag (NM_RASTER_DEBUG: high half = the largest cell) |
 // work items the plan asked for.  Written by the last thread that knows them all.
@@ -1657,12 +1671,9 @@ __device__ __forceinline__ void render_seg(CompLds& L, const RK& k, int nbx, int
   const int tile_x = wk.x % k.gx, tile_y = wk.x / k.gx;
   const long long seg = hdr[9];
   const int tid = threadIdx.x;
-  const int px = tile_x * NM_TILE + (tid & 15), py = tile_y * NM_TILE + (tid >> 4);
-  const bool inside = px < k.W && py < k.H;
+  const auto [px, py, inside, bin, bit, lo] = tile_at(k, nbx, tile_x, tile_y, off);
+  const long long hi = list_end(off, bin, cap);
   const float fxp = (float)px, fyp = (float)py;
-  const int bin = (tile_y / NM_BT) * nbx + tile_x / NM_BT;
-  const uint32_t bit = 1u << ((tile_y % NM_BT) * NM_BT + tile_x % NM_BT);
-  const long long lo = off[bin * NM_NS], hi = min((long long)off[(bin + 1) * NM_NS], cap);
   const long long a = lo + seg_pos[w], b = min(hi, lo + (long long)seg_pos[w + 1]);     // (the plan's boundaries: q * seg by default)
   Pix p = {1.f, 0.f, 0.f, 0.f, 0u, !inside};
   composite_range(L, lo, a, b, bit, keys, vals, recs, (uint32_t)k.K * (uint32_t)sizeof(GRec), fxp, fyp, p);
@@ -1744,12 +1755,9 @@ __global__ void __launch_bounds__(NM_TPB) k_render_fix(RK k, int nbx, const uint
   if (tile_mode[wk.x] != 1u || wk.y >= ns) return;        // finished by its first segment's workgroup / the tile's extra record
   const int tile_x = wk.x % k.gx, tile_y = wk.x / k.gx;
   const int tid = threadIdx.x;
-  const int px = tile_x * NM_TILE + (tid & 15), py = tile_y * NM_TILE + (tid >> 4);
-  const bool inside = px < k.W && py < k.H;
+  const auto [px, py, inside, bin, bit, lo] = tile_at(k, nbx, tile_x, tile_y, off);
+  const long long hi = list_end(off, bin, cap);
   const float fxp = (float)px, fyp = (float)py;
-  const int bin = (tile_y / NM_BT) * nbx + tile_x / NM_BT;
-  const uint32_t bit = 1u << ((tile_y % NM_BT) * NM_BT + tile_x % NM_BT);
-  const long long lo = off[bin * NM_NS], hi = min((long long)off[(bin + 1) * NM_NS], cap);
   FIXDBG(0);
   {
     float Tp = 1.f;
@@ -1814,12 +1822,9 @@ __global__ void __launch_bounds__(NM_TPB) k_render_sum(RK k, int nbx, const uint
   if (tile_mode[t] != 1u) return;
   const uint32_t ns = tile_ns[t], r0 = tile_rec[t];
   const int tid = threadIdx.x;
-  const int px = tile_x * NM_TILE + (tid & 15), py = tile_y * NM_TILE + (tid >> 4);
-  const bool inside = px < k.W && py < k.H;
+  const auto [px, py, inside, bin, bit, lo] = tile_at(k, nbx, tile_x, tile_y, off);
+  const long long hi = list_end(off, bin, cap);
   const float fxp = (float)px, fyp = (float)py;
-  const int bin = (tile_y / NM_BT) * nbx + tile_x / NM_BT;
-  const uint32_t bit = 1u << ((tile_y % NM_BT) * NM_BT + tile_x % NM_BT);
-  const long long lo = off[bin * NM_NS], hi = min((long long)off[(bin + 1) * NM_NS], cap);
   if (tid == 0) s_last = 0u;
   Pix q = {1.f, 0.f, 0.f, 0.f, 0u, !inside};
   for (uint32_t s0 = 0; s0 < ns; s0 += 4) {          // (four records in flight)
@@ -1962,53 +1967,73 @@ __device__ __forceinline__ float wave_sum_dpp(float x) {
 // slot order inside an accumulator row: [0..7] = values of wave_fold8 order, [8] = opacity
 //   v[0]=d/dndc.x v[1]=d/dndc.y v[2]=d/dconic.x v[3]=d/dconic.y v[4]=d/dconic.z v[5..7]=d/drgb
 
-struct BwdLdsR {
+// Reverse compositing comes in two pixel layouts, PX pixels per lane and NW = 4 / PX waves per tile:
+//   PX = 1 (k_render_bwd)    256 threads, lane (x, y) owns pixel (x, y) of the tile.
+//   PX = 2 (k_render_bwd2)   128 threads, lane (x, h) owns the pixels (x, 2h) and (x, 2h + 1), a wave a 16 x 8 block.  The
+//     kernel is instruction-issue bound (§5): with two pixels per lane the per-Gaussian overhead of a wave (record fetch, skip
+//     tests, the fold of the eight partial gradients over the lanes) is paid once for 128 pixels instead of twice, and the
+//     arithmetic in between runs on float2 operands (v_pk_fma_f32 / v_pk_mul_f32: two results for 6.2 cycles against 5.3 for
+//     one).
+template <int PX> using fpx = float __attribute__((ext_vector_type(PX)));
+template <int NW>
+struct BwdLds {
   uint32_t hit[NM_RB_SCAN];
   uint32_t id[NM_RB_BATCH];
-  float acc[4][NM_RB_BATCH * NM_NG];   // one private table per wave: plain stores, no LDS atomics
-  int wcnt[4];
-  uint32_t last[4];
+  float acc[NW][NM_RB_BATCH * NM_NG];   // one private table per wave: plain stores, no LDS atomics
+  int wcnt[NW];
+  uint32_t last[NW];
 };
 // per-pixel state of the reverse walk
+template <int PX>
 struct PixB {
-  float T;                  // transmittance behind the Gaussian about to be visited
-  float T_final;
-  uint32_t last;            // positions > last do not contribute for this pixel
-  float dp0, dp1, dp2;      // dL/dpixel
-  float ar0, ar1, ar2;      // colour composited behind the Gaussian about to be visited (upstream renderCUDA backward: accum_rec)
+  fpx<PX> T;                // transmittance behind the Gaussian about to be visited
+  fpx<PX> T_final;
+  uint32_t last[PX];        // positions > last do not contribute for this pixel
+  fpx<PX> dp0, dp1, dp2;    // dL/dpixel
+  fpx<PX> ar0, ar1, ar2;    // colour composited behind the Gaussian about to be visited (upstream renderCUDA backward: accum_rec)
 };
 // Reverse walk of one tile over list positions (floor, tile_top] of its bin (1-based, counted from lo): the bin's list is
 // examined NM_RB_SCAN candidates at a time, back to front (tile-mask bit test); the survivors are staged in LDS NM_RB_BATCH
-// at a time.  The four per-wave tables are what limits the number of resident tiles (LDS), and this loop lives on latency
-// hiding - 128 per batch = 25 KB per tile = 6 waves per SIMD
-template <bool WITH_OPACITY>
-__device__ __forceinline__ void render_bwd_range(BwdLdsR& L, const RK& k, long long lo, uint32_t floor_pos, uint32_t bit,
+// at a time.  The per-wave tables are what limits the number of resident tiles (LDS), and this loop lives on latency
+// hiding - 128 per batch = 25 KB per tile of four waves = 6 waves per SIMD
+template <int PX, bool WITH_OPACITY>
+__device__ __forceinline__ void render_bwd_range(BwdLds<4 / PX>& L, const RK& k, long long lo, uint32_t floor_pos, uint32_t bit,
                                                  const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ vals,
-                                                 const GRec* __restrict__ recs, float fxp, float fyp, PixB& P,
+                                                 const GRec* __restrict__ recs, float fxp, float fy0, PixB<PX>& P,
                                                  float* __restrict__ acc /* (K, 9) */) {
+  typedef fpx<PX> V;
+  constexpr int NW = 4 / PX, NT = 64 * NW;
+  static_assert(NW == 2 || NW == 4, "the flush sums the wave tables in pairs");
+  static_assert(NT * 16 >= NM_RB_SCAN && NT >= NM_RB_BATCH, "a scan round and the opacity flush are one pass of the workgroup");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float bg_dot = k.bg[0] * P.dp0 + k.bg[1] * P.dp1 + k.bg[2] * P.dp2;
+  const V bg_dot = k.bg[0] * P.dp0 + k.bg[1] * P.dp1 + k.bg[2] * P.dp2;
   const float kx = 0.5f * k.W / NM_LOG2E, ky = 0.5f * k.H / NM_LOG2E;
+  V fy;
+#pragma unroll
+  for (int e = 0; e < PX; ++e) fy[e] = fy0 + (float)e;
   float* my_acc = L.acc[wave];
   // fold slot (value index) of the lanes that end up holding a total:
   const int slot = lane >> 3;           // (wave_fold8_swap: lanes 0, 8, ..., 56 hold values 0..7)
   for (int i = lane; i < NM_RB_BATCH * NM_NG; i += 64) my_acc[i] = 0.f;
   // Gaussians behind every pixel's last contributor (the forward pass stopped compositing there) cannot
   // contribute: the wave skips them before doing any arithmetic, the tile skips whole batches of them
-  uint32_t wave_last = P.last;
+  uint32_t wave_last = P.last[0];
+#pragma unroll
+  for (int e = 1; e < PX; ++e) wave_last = max(wave_last, P.last[e]);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) wave_last = max(wave_last, (uint32_t)__shfl_xor((int)wave_last, o, 64));
   wave_last = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_last);     // (uniform: lets `pos > wave_last` be a scalar branch)
   if (lane == 0) L.last[wave] = wave_last;
   __syncthreads();
-  const uint32_t tile_last = max(max(L.last[0], L.last[1]), max(L.last[2], L.last[3]));
+  uint32_t tile_last = max(L.last[0], L.last[1]);
+  if (NW == 4) tile_last = max(tile_last, max(L.last[2], L.last[3]));
   const long long bottom = lo + (long long)floor_pos;       // absolute index of the first candidate of the range
   for (long long top = lo + (long long)tile_last; top > bottom; top -= NM_RB_SCAN) {
     __syncthreads();
     // ---- candidates top-1, top-2, ... (back to front): which of them touch this tile?  Thread t < 128 looks at sixteen.
     const long long c = top - 1 - 16 * tid;     // this thread's candidates: c, c-1, ..., c-15
     uint32_t m16 = 0;
-    if (tid < NM_RB_SCAN / 16) {
+    if (NT * 16 == NM_RB_SCAN || tid < NM_RB_SCAN / 16) {
       // (the sixteen masks are requested together, a candidate below the range reads the range's first entry and is masked
       //  out: `if (in range && (vals[..] & bit))` sixteen times was sixteen round trips in a row, round 5)
       uint32_t vv[16];
@@ -2019,325 +2044,106 @@ __device__ __forceinline__ void render_bwd_range(BwdLdsR& L, const RK& k, long l
         if (c - q >= bottom && (vv[q] & bit)) m16 |= 1u << q;
     }
     const int mine = __popc(m16);
-    int incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(incl, o, 64); if (lane >= o) incl += y; }
+    const int incl = wave_incl_scan(mine);
     if (lane == 63) L.wcnt[wave] = incl;
     __syncthreads();
     int before = 0, nh = 0;
 #pragma unroll
-    for (int w = 0; w < 4; ++w) { const int n = L.wcnt[w]; before += w < wave ? n : 0; nh += n; }
+    for (int w = 0; w < NW; ++w) { const int n = L.wcnt[w]; before += w < NW - 1 && w < wave ? n : 0; nh += n; }      // (nobody comes behind the last wave)
     {
       int hslot = before + incl - mine;
       for (uint32_t mm = m16; mm; mm &= mm - 1u) L.hit[hslot++] = (uint32_t)(c - (__ffs((int)mm) - 1) - lo) + 1u;   // 1-based, descending
     }
     for (int h0 = 0; h0 < nh; h0 += NM_RB_BATCH) {
-    __syncthreads();
-    const int nb = min(NM_RB_BATCH, nh - h0);
-    // no staging of Gaussian data: every wave keeps the batch's record offsets and list positions in two registers each
-    // (lane l: hits l and l + 64), pulls hit j's out with v_readlane and fetches the record with scalar loads (see GRec)
-    uint32_t offr[NM_RB_BATCH / 64], posr[NM_RB_BATCH / 64];
-#pragma unroll
-    for (int q = 0; q < NM_RB_BATCH / 64; ++q) {      // both groups' keys requested at clamped slots ...
-      posr[q] = L.hit[h0 + min(64 * q + lane, nb - 1)];
-      offr[q] = (uint32_t)keys[lo + posr[q] - 1];
-    }
-#pragma unroll
-    for (int q = 0; q < NM_RB_BATCH / 64; ++q) {
-      const int t = 64 * q + lane;
-      asm volatile("" : "+v"(offr[q]));      // ... and pinned as unconditional (the compiler sinks a conditional load into its branch)
-      const uint32_t id = offr[q];
-      offr[q] = t < nb ? id * (uint32_t)sizeof(GRec) : k.K * (uint32_t)sizeof(GRec);        // padding: the null record ...
-      posr[q] = t < nb ? posr[q] : 0xFFFFFFFFu;                                             // ... behind everything
-      if (t < nb && wave == 0) L.id[t] = id;
-    }
-    auto one = [&](const float4& g0, const float4& g1, const float2& g2, uint32_t pos, int j) {
-      if (pos > wave_last) return;              // wave-uniform: behind every pixel's last contributor
-      const float dx = g0.x - fxp, dy = g0.y - fyp;
-      const float e2 = dx * (g0.z * dx + g0.w * dy) + (g1.x * dy) * dy;      // log2 G
-      const float G = __builtin_amdgcn_exp2f(e2);
-      const float alpha = fminf(0.99f, g2.y * G);
-      const bool act = pos <= P.last && !(e2 > 0.f) && !(alpha < 1.0f / 255.0f);
-      if (__ballot(act) == 0ull) return;      // whole wave skips this Gaussian
-      // Mask-free recurrence: an inactive lane takes part with alpha = 0 - its T (x 1 / (1 - 0)) and its colour behind
-      // (ar <- alpha c + (1 - alpha) ar) stay as they are and every gradient term carries a factor alpha or dL/dalpha, which
-      // is zeroed for it.  Upstream keeps (last_alpha, last_colour) and applies them one Gaussian late; updating `ar` right
-      // after its use is the same recurrence without the two extra state variables and their per-lane selects.
-      const float al = act ? alpha : 0.f;
-      // one hardware reciprocal (1 ulp) for both quotients below: the IEEE divisions were a quarter of the
-      // instructions of an evaluated (pixel, Gaussian) pair; alpha <= 0.99 keeps the denominator >= 0.01
-      const float inv1ma = __builtin_amdgcn_rcpf(1.f - al);
-      P.T = P.T * inv1ma;
-      const float dch = al * P.T;
-      const float c0 = g1.z, c1 = g1.w, c2 = g2.x;
-      float dL_dalpha = (c0 - P.ar0) * P.dp0 + (c1 - P.ar1) * P.dp1 + (c2 - P.ar2) * P.dp2;
-      P.ar0 = al * c0 + (1.f - al) * P.ar0;
-      P.ar1 = al * c1 + (1.f - al) * P.ar1;
-      P.ar2 = al * c2 + (1.f - al) * P.ar2;
-      float g[8];
-      g[5] = dch * P.dp0; g[6] = dch * P.dp1; g[7] = dch * P.dp2;
-      dL_dalpha *= P.T;
-      dL_dalpha += (-P.T_final * inv1ma) * bg_dot;
-      dL_dalpha = act ? dL_dalpha : 0.f;
-      const float dL_dG = g2.y * dL_dalpha;
-      const float Gm = act ? G : 0.f;        // (an inactive lane's G may be inf - e2 > 0 - and 0 x inf would poison the wave's sums)
-      const float gdx = Gm * dx, gdy = Gm * dy;
-      // dG/d(delta) = -G (conic . delta) with conic = -(2a, b, 2c) / log2(e): the 1/log2(e) sits in kx, ky
-      g[0] = dL_dG * (2.f * g0.z * gdx + g0.w * gdy) * kx;   // d/d(ndc x)
-      g[1] = dL_dG * (2.f * g1.x * gdy + g0.w * gdx) * ky;
-      g[2] = -0.5f * gdx * dx * dL_dG;       // d/d conic.x
-      g[3] = -gdx * dy * dL_dG;              // d/d conic.y (full off-diagonal derivative)
-      g[4] = -0.5f * gdy * dy * dL_dG;       // d/d conic.z
-      const float gop = Gm * dL_dalpha;      // d/d opacity
-      // (each Gaussian of a batch is visited once per wave and the table starts from zero: a plain store, no read-modify-write)
-      const float tot = wave_fold8_swap(g, lane);
-      if ((lane & 7) == 0) my_acc[j * NM_NG + slot] = tot;
-      if (WITH_OPACITY) {
-        const float to = wave_sum_dpp(gop);
-        if (lane == 0) my_acc[j * NM_NG + 8] = to;
-      }
-    };
-    struct Set { float4 a[NM_G], b[NM_G]; float2 c[NM_G]; uint32_t pos[NM_G]; };
-    auto fetch = [&](Set& g, uint32_t offs, uint32_t poss, int j0) {
-#pragma unroll
-      for (int u = 0; u < NM_G; ++u) {
-        const char* rp = (const char*)recs + (uint32_t)__builtin_amdgcn_readlane((int)offs, j0 + u);
-        g.a[u] = *(const float4*)rp; g.b[u] = *(const float4*)(rp + 16); g.c[u] = *(const float2*)(rp + 32);
-        g.pos[u] = (uint32_t)__builtin_amdgcn_readlane((int)poss, j0 + u);
-      }
-    };
-#pragma unroll
-    for (int q = 0; q < NM_RB_BATCH / 64; ++q) {
-      const int nq = min(64, nb - 64 * q);          // (wave-uniform)
-      if (nq <= 0) break;
-      Set A, B;
-      fetch(A, offr[q], posr[q], 0);
-      for (int j0 = 0; j0 < nq; j0 += 2 * NM_G) {
-        fetch(B, offr[q], posr[q], j0 + NM_G);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < NM_G; ++u) one(A.a[u], A.b[u], A.c[u], A.pos[u], 64 * q + j0 + u);
-        fetch(A, offr[q], posr[q], (j0 + 2 * NM_G) & 63);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < NM_G; ++u) one(B.a[u], B.b[u], B.c[u], B.pos[u], 64 * q + j0 + NM_G + u);
-      }
-    }
-    __syncthreads();
-    // one global atomic set per (tile, Gaussian): sum the four wave tables; a wave instruction covers eight Gaussians' rows
-    for (int r = tid >> 3; r < nb; r += NM_TPB / 8) {
-      const int o = r * NM_NG + (tid & 7);
-      const float v = (L.acc[0][o] + L.acc[1][o]) + (L.acc[2][o] + L.acc[3][o]);
-      if (v != 0.f) unsafeAtomicAdd(acc + (size_t)L.id[r] * NM_NGS + (tid & 7), v);
-    }
-    if (WITH_OPACITY && tid < nb) {
-      const int o = tid * NM_NG + 8;
-      const float v = (L.acc[0][o] + L.acc[1][o]) + (L.acc[2][o] + L.acc[3][o]);
-      if (v != 0.f) unsafeAtomicAdd(acc + (size_t)L.id[tid] * NM_NGS + 8, v);
-    }
-    __syncthreads();
-    for (int i = lane; i < nb * NM_NG; i += 64) my_acc[i] = 0.f;
-    }
-  }
-}
-
-template <bool WITH_OPACITY>
-__device__ __forceinline__ void bwd_whole(BwdLdsR& L, const RK& k, int nbx, int tile_x, int tile_y, const uint32_t* __restrict__ off,
-                                          const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ vals,
-                                          const uint32_t* __restrict__ tile_rec,
-                                          const GRec* __restrict__ recs, const float* __restrict__ final_T,
-                                          const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix,
-                                          float* __restrict__ acc /* (K, 9) */) {
-  if (tile_rec[tile_y * k.gx + tile_x] != 0xFFFFFFFFu) return;      // bwd_seg
-  const int tid = threadIdx.x;
-  const int px = tile_x * NM_TILE + (tid & 15), py = tile_y * NM_TILE + (tid >> 4);
-  const bool inside = px < k.W && py < k.H;
-  const int bin = (tile_y / NM_BT) * nbx + tile_x / NM_BT;
-  const uint32_t bit = 1u << ((tile_y % NM_BT) * NM_BT + tile_x % NM_BT);
-  const long long lo = off[bin * NM_NS];
-  const size_t pix = (size_t)py * k.W + px, hw = (size_t)k.H * k.W;
-  PixB P = {};
-  if (inside) {
-    P.T_final = final_T[pix];
-    P.last = n_contrib[pix];                       // 1-based position in the bin's list, 0 = none
-    P.dp0 = dL_dpix[pix]; P.dp1 = dL_dpix[hw + pix]; P.dp2 = dL_dpix[2 * hw + pix];
-  }
-  P.T = P.T_final;
-  render_bwd_range<WITH_OPACITY>(L, k, lo, 0u, bit, keys, vals, recs, (float)px, (float)py, P, acc);
-}
-
-// reverse walk of one segment of a candidate tile (k_split_plan), all segments of a tile in parallel.  The state a pixel
-// arrives with at the top of segment s comes from the forward pass's checkpoints: T behind the segment = T in front of
-// segment s+1, colour composited behind it (seen from there) = (C_final - C in front of s+1) / T in front of s+1.  Feeding
-// that colour as the recurrence's `colour behind` makes it start from it.
-template <bool WITH_OPACITY>
-__device__ __forceinline__ void bwd_seg(BwdLdsR& L, const RK& k, int nbx, uint32_t w, const uint32_t* __restrict__ off,
-                                        const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ vals,
-                                        const uint32_t* __restrict__ hdr, const uint32_t* __restrict__ tile_rec,
-                                        const uint32_t* __restrict__ tile_ns, const uint2* __restrict__ work,
-                                        const float4* __restrict__ seg_ct, const uint32_t* __restrict__ seg_pos,
-                                        const GRec* __restrict__ recs, const float* __restrict__ final_T,
-                                        const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix,
-                                        float* __restrict__ acc /* (K, 9) */) {
-  if (w >= hdr[8]) return;
-  const uint2 wk = work[w];
-  const uint32_t seg = hdr[9], sg = wk.y, ns = tile_ns[wk.x], r0 = tile_rec[wk.x];
-  if (sg >= ns) return;            // the tile's extra record
-  const int tile_x = wk.x % k.gx, tile_y = wk.x / k.gx;
-  const int tid = threadIdx.x;
-  const int px = tile_x * NM_TILE + (tid & 15), py = tile_y * NM_TILE + (tid >> 4);
-  const bool inside = px < k.W && py < k.H;
-  const int bin = (tile_y / NM_BT) * nbx + tile_x / NM_BT;
-  const uint32_t bit = 1u << ((tile_y % NM_BT) * NM_BT + tile_x % NM_BT);
-  const long long lo = off[bin * NM_NS];
-  const size_t pix = (size_t)py * k.W + px, hw = (size_t)k.H * k.W;
-  const uint32_t floor_pos = seg_pos[r0 + sg], ceil_pos = seg_pos[r0 + sg + 1];      // the segment holds positions floor_pos+1 .. ceil_pos
-  if (ceil_pos <= floor_pos) return;                                                   // (an empty segment: the walk passed two nominal starts in one batch)
-  PixB P = {};
-  uint32_t last = 0u;
-  if (inside) {
-    P.T_final = final_T[pix];
-    last = n_contrib[pix];
-    P.dp0 = dL_dpix[pix]; P.dp1 = dL_dpix[hw + pix]; P.dp2 = dL_dpix[2 * hw + pix];
-  }
-  P.T = P.T_final;
-  if (last > ceil_pos) {            // the pixel's last contributor lies in a later segment
-    const float4 nx = seg_ct[(size_t)(r0 + sg + 1) * NM_TPB + tid], fin = seg_ct[(size_t)(r0 + ns) * NM_TPB + tid];
-    const float inv = 1.f / nx.w;
-    P.T = nx.w;
-    P.ar0 = (fin.x - nx.x) * inv; P.ar1 = (fin.y - nx.y) * inv; P.ar2 = (fin.z - nx.z) * inv;
-    P.last = ceil_pos;
-  } else {
-    P.last = last > floor_pos ? last : 0u;      // ends in this segment, or in an earlier one (nothing to do here)
-  }
-  render_bwd_range<WITH_OPACITY>(L, k, lo, floor_pos, bit, keys, vals, recs, (float)px, (float)py, P, acc);
-}
-
-// ---------------------------------------------------------------- reverse compositing, two pixels per lane
-// The same walk with 128 threads per tile: lane (x, h) owns the pixels (x, 2h) and (x, 2h + 1) of the tile, a wave a 16 x 8
-// block.  The kernel is instruction-issue bound (§5): with two pixels per lane the per-Gaussian overhead of a wave (record
-// fetch, skip tests, the fold of the eight partial gradients over the lanes) is paid once for 128 pixels instead of twice,
-// and the arithmetic in between runs on float2 operands (v_pk_fma_f32 / v_pk_mul_f32: two results for 6.2 cycles against
-// 5.3 for one).  Per pixel the expressions are those of render_bwd_range, element by element.
-typedef float f2r __attribute__((ext_vector_type(2)));
-struct BwdLdsR2 {
-  uint32_t hit[NM_RB_SCAN];
-  uint32_t id[NM_RB_BATCH];
-  float acc[2][NM_RB_BATCH * NM_NG];
-  int wcnt[2];
-  uint32_t last[2];
-};
-struct PixB2 {
-  f2r T, T_final;
-  uint32_t last[2];
-  f2r dp0, dp1, dp2, ar0, ar1, ar2;
-};
-template <bool WITH_OPACITY>
-__device__ __forceinline__ void render_bwd_range2(BwdLdsR2& L, const RK& k, long long lo, uint32_t floor_pos, uint32_t bit,
-                                                  const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ vals,
-                                                  const GRec* __restrict__ recs, float fxp, float fy0, PixB2& P,
-                                                  float* __restrict__ acc /* (K, 9) */) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const f2r bg_dot = k.bg[0] * P.dp0 + k.bg[1] * P.dp1 + k.bg[2] * P.dp2;
-  const float kx = 0.5f * k.W / NM_LOG2E, ky = 0.5f * k.H / NM_LOG2E;
-  const f2r fy = {fy0, fy0 + 1.f};
-  float* my_acc = L.acc[wave];
-  const int slot = lane >> 3;           // (wave_fold8_swap: lanes 0, 8, ..., 56 hold values 0..7)
-  for (int i = lane; i < NM_RB_BATCH * NM_NG; i += 64) my_acc[i] = 0.f;
-  uint32_t wave_last = max(P.last[0], P.last[1]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) wave_last = max(wave_last, (uint32_t)__shfl_xor((int)wave_last, o, 64));
-  wave_last = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_last);
-  if (lane == 0) L.last[wave] = wave_last;
-  __syncthreads();
-  const uint32_t tile_last = max(L.last[0], L.last[1]);
-  const long long bottom = lo + (long long)floor_pos;
-  for (long long top = lo + (long long)tile_last; top > bottom; top -= NM_RB_SCAN) {
-    __syncthreads();
-    const long long c = top - 1 - 16 * tid;     // this thread's candidates: c, c-1, ..., c-15 (128 threads x 16 = NM_RB_SCAN)
-    uint32_t m16 = 0;
-    uint32_t vv[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) vv[q] = vals[max(c - q, bottom)];
-#pragma unroll
-    for (int q = 0; q < 16; ++q)
-      if (c - q >= bottom && (vv[q] & bit)) m16 |= 1u << q;
-    const int mine = __popc(m16);
-    int incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(incl, o, 64); if (lane >= o) incl += y; }
-    if (lane == 63) L.wcnt[wave] = incl;
-    __syncthreads();
-    const int n0 = L.wcnt[0], nh = n0 + L.wcnt[1];
-    {
-      int hslot = (wave ? n0 : 0) + incl - mine;
-      for (uint32_t mm = m16; mm; mm &= mm - 1u) L.hit[hslot++] = (uint32_t)(c - (__ffs((int)mm) - 1) - lo) + 1u;   // 1-based, descending
-    }
-    for (int h0 = 0; h0 < nh; h0 += NM_RB_BATCH) {
       __syncthreads();
       const int nb = min(NM_RB_BATCH, nh - h0);
+      // no staging of Gaussian data: every wave keeps the batch's record offsets and list positions in two registers each
+      // (lane l: hits l and l + 64), pulls hit j's out with v_readlane and fetches the record with scalar loads (see GRec)
       uint32_t offr[NM_RB_BATCH / 64], posr[NM_RB_BATCH / 64];
 #pragma unroll
-      for (int q = 0; q < NM_RB_BATCH / 64; ++q) {
+      for (int q = 0; q < NM_RB_BATCH / 64; ++q) {      // both groups' keys requested at clamped slots ...
         posr[q] = L.hit[h0 + min(64 * q + lane, nb - 1)];
         offr[q] = (uint32_t)keys[lo + posr[q] - 1];
       }
 #pragma unroll
       for (int q = 0; q < NM_RB_BATCH / 64; ++q) {
         const int t = 64 * q + lane;
-        asm volatile("" : "+v"(offr[q]));
+        asm volatile("" : "+v"(offr[q]));      // ... and pinned as unconditional (the compiler sinks a conditional load into its branch)
         const uint32_t id = offr[q];
         offr[q] = t < nb ? id * (uint32_t)sizeof(GRec) : k.K * (uint32_t)sizeof(GRec);        // padding: the null record ...
         posr[q] = t < nb ? posr[q] : 0xFFFFFFFFu;                                             // ... behind everything
         if (t < nb && wave == 0) L.id[t] = id;
       }
+      // one Gaussian against the lane's PX pixels, element by element the forward pass's expressions
       auto one = [&](const float4& g0, const float4& g1, const float2& g2, uint32_t pos, int j) {
         if (pos > wave_last) return;              // wave-uniform: behind every pixel's last contributor
-        const float dxs = g0.x - fxp;
-        const f2r dx = {dxs, dxs};
-        const f2r dy = g0.y - fy;
-        const f2r e2 = dx * (g0.z * dx + g0.w * dy) + (g1.x * dy) * dy;      // log2 G, element by element as in the forward pass
-        f2r G;
-        G[0] = __builtin_amdgcn_exp2f(e2[0]); G[1] = __builtin_amdgcn_exp2f(e2[1]);
-        f2r alpha = g2.y * G;
-        alpha[0] = fminf(0.99f, alpha[0]); alpha[1] = fminf(0.99f, alpha[1]);
-        const bool act0 = pos <= P.last[0] && !(e2[0] > 0.f) && !(alpha[0] < 1.0f / 255.0f);
-        const bool act1 = pos <= P.last[1] && !(e2[1] > 0.f) && !(alpha[1] < 1.0f / 255.0f);
-        if (__ballot(act0 || act1) == 0ull) return;      // whole wave skips this Gaussian
-        // mask-free recurrence (see render_bwd_range): an inactive pixel takes part with alpha = 0
-        f2r al;
-        al[0] = act0 ? alpha[0] : 0.f; al[1] = act1 ? alpha[1] : 0.f;
-        const f2r oma = 1.f - al;
-        f2r inv1ma;
-        inv1ma[0] = __builtin_amdgcn_rcpf(oma[0]); inv1ma[1] = __builtin_amdgcn_rcpf(oma[1]);
+        const V dx = (V)(g0.x - fxp), dy = g0.y - fy;
+        const V e2 = dx * (g0.z * dx + g0.w * dy) + (g1.x * dy) * dy;      // log2 G
+        V G;
+#pragma unroll
+        for (int e = 0; e < PX; ++e) G[e] = __builtin_amdgcn_exp2f(e2[e]);
+        V alpha = g2.y * G;
+#pragma unroll
+        for (int e = 0; e < PX; ++e) alpha[e] = fminf(0.99f, alpha[e]);
+        bool act[PX], any = false;
+#pragma unroll
+        for (int e = 0; e < PX; ++e) {
+          act[e] = pos <= P.last[e] && !(e2[e] > 0.f) && !(alpha[e] < 1.0f / 255.0f);
+          any = any || act[e];
+        }
+        if (__ballot(any) == 0ull) return;      // whole wave skips this Gaussian
+        // Mask-free recurrence: an inactive pixel takes part with alpha = 0 - its T (x 1 / (1 - 0)) and its colour behind
+        // (ar <- alpha c + (1 - alpha) ar) stay as they are and every gradient term carries a factor alpha or dL/dalpha, which
+        // is zeroed for it.  Upstream keeps (last_alpha, last_colour) and applies them one Gaussian late; updating `ar` right
+        // after its use is the same recurrence without the two extra state variables and their per-lane selects.
+        V al;
+#pragma unroll
+        for (int e = 0; e < PX; ++e) al[e] = act[e] ? alpha[e] : 0.f;
+        const V oma = 1.f - al;
+        // one hardware reciprocal (1 ulp) for both quotients below: the IEEE divisions were a quarter of the
+        // instructions of an evaluated (pixel, Gaussian) pair; alpha <= 0.99 keeps the denominator >= 0.01
+        V inv1ma;
+#pragma unroll
+        for (int e = 0; e < PX; ++e) inv1ma[e] = __builtin_amdgcn_rcpf(oma[e]);
         P.T = P.T * inv1ma;
-        const f2r dch = al * P.T;
+        const V dch = al * P.T;
         const float c0 = g1.z, c1 = g1.w, c2 = g2.x;
-        f2r dL_dalpha = (c0 - P.ar0) * P.dp0 + (c1 - P.ar1) * P.dp1 + (c2 - P.ar2) * P.dp2;
+        V dL_dalpha = (c0 - P.ar0) * P.dp0 + (c1 - P.ar1) * P.dp1 + (c2 - P.ar2) * P.dp2;
         P.ar0 = al * c0 + oma * P.ar0;
         P.ar1 = al * c1 + oma * P.ar1;
         P.ar2 = al * c2 + oma * P.ar2;
-        const f2r q5 = dch * P.dp0, q6 = dch * P.dp1, q7 = dch * P.dp2;
+        V q[8];
+        q[5] = dch * P.dp0; q[6] = dch * P.dp1; q[7] = dch * P.dp2;
         dL_dalpha *= P.T;
         dL_dalpha += (-P.T_final * inv1ma) * bg_dot;
-        dL_dalpha[0] = act0 ? dL_dalpha[0] : 0.f; dL_dalpha[1] = act1 ? dL_dalpha[1] : 0.f;
-        const f2r dL_dG = g2.y * dL_dalpha;
-        f2r Gm;        // (an inactive pixel's G may be inf - e2 > 0 - and 0 x inf would poison the sums)
-        Gm[0] = act0 ? G[0] : 0.f; Gm[1] = act1 ? G[1] : 0.f;
-        const f2r gdx = Gm * dx, gdy = Gm * dy;
-        const f2r q0 = dL_dG * (2.f * g0.z * gdx + g0.w * gdy) * kx;   // d/d(ndc x)
-        const f2r q1 = dL_dG * (2.f * g1.x * gdy + g0.w * gdx) * ky;
-        const f2r q2 = -0.5f * gdx * dx * dL_dG;       // d/d conic.x
-        const f2r q3 = -gdx * dy * dL_dG;              // d/d conic.y
-        const f2r q4 = -0.5f * gdy * dy * dL_dG;       // d/d conic.z
-        float g[8];
-        g[0] = q0[0] + q0[1]; g[1] = q1[0] + q1[1]; g[2] = q2[0] + q2[1]; g[3] = q3[0] + q3[1];
-        g[4] = q4[0] + q4[1]; g[5] = q5[0] + q5[1]; g[6] = q6[0] + q6[1]; g[7] = q7[0] + q7[1];
+#pragma unroll
+        for (int e = 0; e < PX; ++e) dL_dalpha[e] = act[e] ? dL_dalpha[e] : 0.f;
+        const V dL_dG = g2.y * dL_dalpha;
+        V Gm;        // (an inactive pixel's G may be inf - e2 > 0 - and 0 x inf would poison the wave's sums)
+#pragma unroll
+        for (int e = 0; e < PX; ++e) Gm[e] = act[e] ? G[e] : 0.f;
+        const V gdx = Gm * dx, gdy = Gm * dy;
+        // dG/d(delta) = -G (conic . delta) with conic = -(2a, b, 2c) / log2(e): the 1/log2(e) sits in kx, ky
+        q[0] = dL_dG * (2.f * g0.z * gdx + g0.w * gdy) * kx;   // d/d(ndc x)
+        q[1] = dL_dG * (2.f * g1.x * gdy + g0.w * gdx) * ky;
+        q[2] = -0.5f * gdx * dx * dL_dG;       // d/d conic.x
+        q[3] = -gdx * dy * dL_dG;              // d/d conic.y (full off-diagonal derivative)
+        q[4] = -0.5f * gdy * dy * dL_dG;       // d/d conic.z
+        V qop = Gm * dL_dalpha;                // d/d opacity
+        float g[8], gop = qop[0];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          g[i] = q[i][0];
+#pragma unroll
+          for (int e = 1; e < PX; ++e) g[i] += q[i][e];
+        }
+#pragma unroll
+        for (int e = 1; e < PX; ++e) gop += qop[e];
+        // (each Gaussian of a batch is visited once per wave and the table starts from zero: a plain store, no read-modify-write)
         const float tot = wave_fold8_swap(g, lane);
         if ((lane & 7) == 0) my_acc[j * NM_NG + slot] = tot;
         if (WITH_OPACITY) {
-          const f2r gop = Gm * dL_dalpha;      // d/d opacity
-          const float to = wave_sum_dpp(gop[0] + gop[1]);
+          const float to = wave_sum_dpp(gop);
           if (lane == 0) my_acc[j * NM_NG + 8] = to;
         }
       };
@@ -2368,15 +2174,18 @@ __device__ __forceinline__ void render_bwd_range2(BwdLdsR2& L, const RK& k, long
         }
       }
       __syncthreads();
-      // one global atomic set per (tile, Gaussian): sum the two wave tables
-      for (int r = tid >> 3; r < nb; r += 16) {
-        const int o = r * NM_NG + (tid & 7);
-        const float v = L.acc[0][o] + L.acc[1][o];
+      // one global atomic set per (tile, Gaussian): sum the wave tables; a wave instruction covers eight Gaussians' rows
+      auto table_sum = [&](int o) {
+        float v = L.acc[0][o] + L.acc[1][o];
+        if (NW == 4) v += L.acc[2][o] + L.acc[3][o];
+        return v;
+      };
+      for (int r = tid >> 3; r < nb; r += NT / 8) {
+        const float v = table_sum(r * NM_NG + (tid & 7));
         if (v != 0.f) unsafeAtomicAdd(acc + (size_t)L.id[r] * NM_NGS + (tid & 7), v);
       }
       if (WITH_OPACITY && tid < nb) {
-        const int o = tid * NM_NG + 8;
-        const float v = L.acc[0][o] + L.acc[1][o];
+        const float v = table_sum(tid * NM_NG + 8);
         if (v != 0.f) unsafeAtomicAdd(acc + (size_t)L.id[tid] * NM_NGS + 8, v);
       }
       __syncthreads();
@@ -2385,19 +2194,24 @@ __device__ __forceinline__ void render_bwd_range2(BwdLdsR2& L, const RK& k, long
   }
 }
 
-// the state the two pixels of a lane arrive with: whole tile (segment == nullptr) or the segment [floor_pos, ceil_pos) of a
-// split tile, from the forward pass's checkpoints (see bwd_seg)
-template <bool WITH_OPACITY>
-__global__ void __launch_bounds__(128) k_render_bwd2(RK k, int nbx, int ntile, const uint32_t* __restrict__ off,
-                                                     const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ vals,
-                                                     const uint32_t* __restrict__ hdr, const uint32_t* __restrict__ tile_rec,
-                                                     const uint32_t* __restrict__ tile_ns, const uint2* __restrict__ work,
-                                                     const float4* __restrict__ seg_ct, const uint32_t* __restrict__ seg_pos,
-                                                     const GRec* __restrict__ recs, const float* __restrict__ final_T,
-                                                     const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix,
-                                                     float* __restrict__ acc /* (K, 9) */) {
-  __shared__ BwdLdsR2 L;
-  if (hdr[3]) return;          // (overflowed render: no gradient, see k_render_bwd)
+// Reverse walk of workgroup b of the 1-D grid: workgroups [0, ntile) = whole tiles, the others = the segments of the candidate
+// tiles (k_split_plan), all segments of a tile in parallel, side by side with the whole tiles.  The state a pixel arrives with
+// at the top of segment s comes from the forward pass's checkpoints: T behind the segment = T in front of segment s+1, colour
+// composited behind it (seen from there) = (C_final - C in front of s+1) / T in front of s+1.  Feeding that colour as the
+// recurrence's `colour behind` makes it start from it.
+template <int PX, bool WITH_OPACITY>
+__device__ __forceinline__ void render_bwd_tile(BwdLds<4 / PX>& L, const RK& k, int nbx, int ntile, const uint32_t* __restrict__ off,
+                                                const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ vals,
+                                                const uint32_t* __restrict__ hdr, const uint32_t* __restrict__ tile_rec,
+                                                const uint32_t* __restrict__ tile_ns, const uint2* __restrict__ work,
+                                                const float4* __restrict__ seg_ct, const uint32_t* __restrict__ seg_pos,
+                                                const GRec* __restrict__ recs, const float* __restrict__ final_T,
+                                                const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix,
+                                                float* __restrict__ acc /* (K, 9) */) {
+  // A render whose bin lists overflowed composited the background only and left lists / checkpoints unwritten: it contributes
+  // no gradient (the accumulators stay zero).  The host learns of the overflow from the status words and raises; this guard
+  // is what lets it do so without stalling the reverse sweep on the forward pass's completion.
+  if (hdr[3]) return;
   const int b = blockIdx.x;
   int tile;
   bool seg = false;
@@ -2414,24 +2228,21 @@ __global__ void __launch_bounds__(128) k_render_bwd2(RK k, int nbx, int ntile, c
     seg = true;
   }
   const int tile_x = tile % k.gx, tile_y = tile / k.gx;
+  const TileAt t = tile_at<PX>(k, nbx, tile_x, tile_y, off);
   const int tid = threadIdx.x;
-  const int px = tile_x * NM_TILE + (tid & 15), py = tile_y * NM_TILE + 2 * (tid >> 4);
-  const int bin = (tile_y / NM_BT) * nbx + tile_x / NM_BT;
-  const uint32_t bit = 1u << ((tile_y % NM_BT) * NM_BT + tile_x % NM_BT);
-  const long long lo = off[bin * NM_NS];
   const size_t hw = (size_t)k.H * k.W;
   uint32_t floor_pos = 0u, ceil_pos = 0xFFFFFFFFu;
   if (seg) {
     floor_pos = seg_pos[r0 + sg]; ceil_pos = seg_pos[r0 + sg + 1];      // the segment holds positions floor_pos+1 .. ceil_pos
-    if (ceil_pos <= floor_pos) return;
+    if (ceil_pos <= floor_pos) return;                                  // (an empty segment: the walk passed two nominal starts in one batch)
   }
-  PixB2 P = {};
+  PixB<PX> P = {};
 #pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const bool inside = px < k.W && py + e < k.H;
+  for (int e = 0; e < PX; ++e) {
+    const bool inside = t.px < k.W && t.py + e < k.H;
     uint32_t last = 0u;
     if (inside) {
-      const size_t pix = (size_t)(py + e) * k.W + px;
+      const size_t pix = (size_t)(t.py + e) * k.W + t.px;
       P.T_final[e] = final_T[pix];
       last = n_contrib[pix];                       // 1-based position in the bin's list, 0 = none
       P.dp0[e] = dL_dpix[pix]; P.dp1[e] = dL_dpix[hw + pix]; P.dp2[e] = dL_dpix[2 * hw + pix];
@@ -2440,7 +2251,7 @@ __global__ void __launch_bounds__(128) k_render_bwd2(RK k, int nbx, int ntile, c
     if (!seg) {
       P.last[e] = last;
     } else if (last > ceil_pos) {            // the pixel's last contributor lies in a later segment
-      const int pin = (2 * (tid >> 4) + e) * NM_TILE + (tid & 15);      // the pixel's index in its tile (the forward pass's thread)
+      const int pin = (PX * (tid >> 4) + e) * NM_TILE + (tid & 15);      // the pixel's index in its tile (the forward pass's thread)
       const float4 nx = seg_ct[(size_t)(r0 + sg + 1) * NM_TPB + pin], fin = seg_ct[(size_t)(r0 + ns) * NM_TPB + pin];
       const float inv = 1.f / nx.w;
       P.T[e] = nx.w;
@@ -2450,10 +2261,10 @@ __global__ void __launch_bounds__(128) k_render_bwd2(RK k, int nbx, int ntile, c
       P.last[e] = last > floor_pos ? last : 0u;      // ends in this segment, or in an earlier one (nothing to do here)
     }
   }
-  render_bwd_range2<WITH_OPACITY>(L, k, lo, floor_pos, bit, keys, vals, recs, (float)px, (float)py, P, acc);
+  render_bwd_range<PX, WITH_OPACITY>(L, k, t.lo, floor_pos, t.bit, keys, vals, recs, (float)t.px, (float)t.py, P, acc);
 }
 
-// one launch, 1-D grid: workgroups [0, ntile) = whole tiles, the others = segments of the candidate tiles, side by side
+// the two layouts as kernels of their own: a lone view (one pixel per lane) and views sharing the chip (two), see nm_raster_backward
 template <bool WITH_OPACITY>
 __global__ void __launch_bounds__(NM_TPB) k_render_bwd(RK k, int nbx, int ntile, const uint32_t* __restrict__ off,
                                                        const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ vals,
@@ -2463,17 +2274,22 @@ __global__ void __launch_bounds__(NM_TPB) k_render_bwd(RK k, int nbx, int ntile,
                                                        const GRec* __restrict__ recs, const float* __restrict__ final_T,
                                                        const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix,
                                                        float* __restrict__ acc /* (K, 9) */) {
-  __shared__ BwdLdsR L;
-  const int b = blockIdx.x;
-  // A render whose bin lists overflowed composited the background only and left lists / checkpoints unwritten: it contributes
-  // no gradient (the accumulators stay zero).  The host learns of the overflow from the status words and raises; this guard
-  // is what lets it do so without stalling the reverse sweep on the forward pass's completion.
-  if (hdr[3]) return;
-  if (b < ntile)
-    bwd_whole<WITH_OPACITY>(L, k, nbx, b % k.gx, b / k.gx + k.ty0, off, keys, vals, tile_rec, recs, final_T, n_contrib, dL_dpix, acc);
-  else
-    bwd_seg<WITH_OPACITY>(L, k, nbx, (uint32_t)(b - ntile), off, keys, vals, hdr, tile_rec, tile_ns, work, seg_ct, seg_pos, recs,
-                          final_T, n_contrib, dL_dpix, acc);
+  __shared__ BwdLds<4> L;
+  render_bwd_tile<1, WITH_OPACITY>(L, k, nbx, ntile, off, keys, vals, hdr, tile_rec, tile_ns, work, seg_ct, seg_pos, recs, final_T,
+                                   n_contrib, dL_dpix, acc);
+}
+template <bool WITH_OPACITY>
+__global__ void __launch_bounds__(128) k_render_bwd2(RK k, int nbx, int ntile, const uint32_t* __restrict__ off,
+                                                     const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ vals,
+                                                     const uint32_t* __restrict__ hdr, const uint32_t* __restrict__ tile_rec,
+                                                     const uint32_t* __restrict__ tile_ns, const uint2* __restrict__ work,
+                                                     const float4* __restrict__ seg_ct, const uint32_t* __restrict__ seg_pos,
+                                                     const GRec* __restrict__ recs, const float* __restrict__ final_T,
+                                                     const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix,
+                                                     float* __restrict__ acc /* (K, 9) */) {
+  __shared__ BwdLds<2> L;
+  render_bwd_tile<2, WITH_OPACITY>(L, k, nbx, ntile, off, keys, vals, hdr, tile_rec, tile_ns, work, seg_ct, seg_pos, recs, final_T,
+                                   n_contrib, dL_dpix, acc);
 }
 
 // adjoint of k_preprocess: per-Gaussian chain rule to means3D / cov3D / SH (upstream computeCov2DCUDA +
@@ -2900,26 +2716,16 @@ extern "C" int nm_raster_backward(const nm_raster_cfg* cfg, int32_t K, int32_t m
   // (nm_raster_set_reverse_px2; SceneRuntime sets it with its view streams); NM_BWD_PX2 overrides, read per call (tests, A/B).
   const char* px2_env = getenv("NM_BWD_PX2");
   const bool px2 = px2_env ? atoi(px2_env) != 0 : g_bwd_px2 != 0;
-  if (px2 && dL_dopacity)
-    NM_LAUNCH(k_render_bwd2<true>, dim3(ntile + t.items), dim3(128), 0, s, k, t.nbx, ntile, (const uint32_t*)t.off,
-              (const unsigned long long*)t.keys, (const uint32_t*)t.vals, (const uint32_t*)t.hdr, (const uint32_t*)t.tile_rec,
-              (const uint32_t*)t.tile_ns, (const uint2*)t.work, (const float4*)t.seg_ct, (const uint32_t*)t.seg_pos, (const GRec*)t.recs,
-              t.final_T, t.n_contrib, dL_dcolor, acc);
-  else if (px2)
-    NM_LAUNCH(k_render_bwd2<false>, dim3(ntile + t.items), dim3(128), 0, s, k, t.nbx, ntile, (const uint32_t*)t.off,
-              (const unsigned long long*)t.keys, (const uint32_t*)t.vals, (const uint32_t*)t.hdr, (const uint32_t*)t.tile_rec,
-              (const uint32_t*)t.tile_ns, (const uint2*)t.work, (const float4*)t.seg_ct, (const uint32_t*)t.seg_pos, (const GRec*)t.recs,
-              t.final_T, t.n_contrib, dL_dcolor, acc);
-  else if (dL_dopacity)
-    NM_LAUNCH(k_render_bwd<true>, dim3(ntile + t.items), dim3(NM_TPB), 0, s, k, t.nbx, ntile, (const uint32_t*)t.off,
-              (const unsigned long long*)t.keys, (const uint32_t*)t.vals, (const uint32_t*)t.hdr, (const uint32_t*)t.tile_rec,
-              (const uint32_t*)t.tile_ns, (const uint2*)t.work, (const float4*)t.seg_ct, (const uint32_t*)t.seg_pos, (const GRec*)t.recs,
-              t.final_T, t.n_contrib, dL_dcolor, acc);
-  else
-    NM_LAUNCH(k_render_bwd<false>, dim3(ntile + t.items), dim3(NM_TPB), 0, s, k, t.nbx, ntile, (const uint32_t*)t.off,
-              (const unsigned long long*)t.keys, (const uint32_t*)t.vals, (const uint32_t*)t.hdr, (const uint32_t*)t.tile_rec,
-              (const uint32_t*)t.tile_ns, (const uint2*)t.work, (const float4*)t.seg_ct, (const uint32_t*)t.seg_pos, (const GRec*)t.recs,
-              t.final_T, t.n_contrib, dL_dcolor, acc);
+#define NM_BWD_LAUNCH(kern, nt)                                                                                                  \
+  NM_LAUNCH(kern, dim3(ntile + t.items), dim3(nt), 0, s, k, t.nbx, ntile, (const uint32_t*)t.off,                               \
+            (const unsigned long long*)t.keys, (const uint32_t*)t.vals, (const uint32_t*)t.hdr, (const uint32_t*)t.tile_rec,    \
+            (const uint32_t*)t.tile_ns, (const uint2*)t.work, (const float4*)t.seg_ct, (const uint32_t*)t.seg_pos,              \
+            (const GRec*)t.recs, t.final_T, t.n_contrib, dL_dcolor, acc)
+  if (px2 && dL_dopacity) NM_BWD_LAUNCH(k_render_bwd2<true>, 128);
+  else if (px2) NM_BWD_LAUNCH(k_render_bwd2<false>, 128);
+  else if (dL_dopacity) NM_BWD_LAUNCH(k_render_bwd<true>, NM_TPB);
+  else NM_BWD_LAUNCH(k_render_bwd<false>, NM_TPB);
+#undef NM_BWD_LAUNCH
   NM_LAUNCH_CHECK();
   NM_LAUNCH(k_preprocess_bwd, dim3(nm_div_up(K, 256)), dim3(256), 0, s, k, K, means3D, shs, cov3D, (const int*)t.rad, t.clamped, acc,
             dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dopacity, dL_dshs, dL_dcolors, shs ? 1 : 0);
