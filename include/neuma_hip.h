@@ -535,6 +535,23 @@ int nm_regist_backward(int32_t k, const float* xyz, const float* log_scales, con
                        float scale_modifier, const float* dL_dmeans3D, const float* dL_dcov6, float* dL_dparams,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* SH colour coefficients rotated with the Gaussians (transform_shs_by_rotmat, modules/d3gs/utils/transform_utils.py:41-104):
+ * shs_out[g, :, ch] = diag(1, D_1, D_2, D_3)(R) shs_in[g, :, ch], D defined by sum_j c'_j Y_j(R d) = sum_j c_j Y_j(d) for
+ * the rasterizer's basis Y, built from R as a polynomial (sh_rotation_matrices of render/transform_utils.py is the same
+ * formula).  R: 9 DEVICE floats, row-major, as in `points @ R^T` (= params[0:9] of nm_regist_apply).  shs (k, n_coeff, 3):
+ * n_coeff = 4 | 9 | 16 with has_dc = 1 (row 0, the DC term, is copied) or 3 | 8 | 15 with has_dc = 0 (a bare
+ * _features_rest); any other count is NM_ERR_INVALID.  shs_out may alias shs_in. */
+int nm_sh_rotate(int32_t k, int32_t n_coeff, int32_t has_dc, const float* R, const float* shs_in, float* shs_out, void* stream);
+
+/* Adjoint of nm_sh_rotate: dL_dR (9 DEVICE floats) += sum over the Gaussians and channels, chained from the <= 83 entries of
+ * dL/dD through the polynomial; dL_dshs_in (k, n_coeff, 3) = D^T dL_dshs_out (DC row copied), may be NULL, may alias
+ * dL_dshs_out.  fp64 partials per workgroup, summed by one workgroup in a fixed order, no atomics: bitwise reproducible.
+ * workspace: nm_sh_rotate_bwd_workspace(k) bytes of device scratch. */
+size_t nm_sh_rotate_bwd_workspace(int32_t k);
+int nm_sh_rotate_backward(int32_t k, int32_t n_coeff, int32_t has_dc, const float* R, const float* shs_in,
+                          const float* dL_dshs_out, float* dL_dR, float* dL_dshs_in, void* workspace, size_t workspace_bytes,
+                          void* stream);
+
 /* SSIM loss (modules/d3gs/utils/loss_utils.py:26-66, window 11, sigma 1.5, zero padding, size_average) of two (3,H,W) fp32
  * images: *loss_out (device float) += weight * (1 - ssim(img, gt)); dL_dimg (may be NULL) += weight * d(1 - ssim)/dimg.
  * Adds to both, so it composes with nm_pixel_loss called first.  The loss value is deterministic (fixed-order fp64

@@ -137,6 +137,9 @@ SIGNATURES = {
     "nm_regist_apply": (C.c_int, [_I32, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P]),
     "nm_regist_bwd_workspace": (_SZ, [_I32]),
     "nm_regist_backward": (C.c_int, [_I32, _P, _P, _P, _P, _F, _P, _P, _P, _P, _SZ, _P]),
+    "nm_sh_rotate": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P]),
+    "nm_sh_rotate_bwd_workspace": (_SZ, [_I32]),
+    "nm_sh_rotate_backward": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "nm_ssim_workspace": (_SZ, [_I32, _I32]),
     "nm_ssim_loss": (C.c_int, [_F, _I32, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
     "nm_image_metrics_workspace": (_SZ, [_I32, _I32, _I32, _I32]),

@@ -11,8 +11,11 @@ Outputs in <assets_root>/<sim_data_name>/ (what finetune-<obj>.yaml points at):
 Per iteration the reference runs the transform in torch autograd, 3 renders forward + backward, l1 + lambda (1 - ssim) and a
 `loss.item()`.  Here (NativeRegistration): nm_regist_apply, per view raster_forward_raw -> nm_pixel_loss -> nm_ssim_loss ->
 raster_backward_raw -> nm_regist_backward into 17 device scalars (dR, dq_R, ds, dt), torch autograd from those to r, t, s only,
-RAdam + the cosine schedule; the loss goes to a device history that is read at the end.  `regist_step_torch` is the same
-iteration through the differentiable torch path (build_cov3D + GaussianRasterizer + tune.ssim).
+RAdam + the cosine schedule; the loss goes to a device history that is read at the end.  With sh_degree > 0 the colour
+coefficients turn with the Gaussians (register.py:68-91, transform_shs_by_quat): one nm_sh_rotate per iteration with the R the
+loop already packed, and per view nm_sh_rotate_backward adds the colour gradient's share into the same dR.  `regist_step_torch`
+is the same iteration through the differentiable torch path (build_cov3D + GaussianRasterizer + tune.ssim +
+transform_utils.rotate_shs_torch).
 
 Rotation conversions follow pytorch3d.transforms' published conventions (wxyz quaternions, Gram-Schmidt 6D rows, the
 best-conditioned candidate of matrix_to_quaternion, standardised to a non-negative real part)."""
@@ -176,9 +179,11 @@ class Register(nn.Module):
     def get_rotmat(self):
         return rot6d_to_rotmat(self.r)
 
-    def forward(self, points: Tensor, scales: Tensor, rotations: Tensor, scaling_modifier: float = 1.0):
+    def forward(self, points: Tensor, scales: Tensor, rotations: Tensor, scaling_modifier: float = 1.0,
+                f_rest: Optional[Tensor] = None):
         """register.py forward (points / log-scales / quaternions as loaded) + the covariance build, differentiable in r, t,
-        s.  Returns points, scales (log), rotations (normalised), cov3D (K,6) and origin (1,3)."""
+        s.  Returns points, scales (log), rotations (normalised), cov3D (K,6) and origin (1,3); with `f_rest` (K, 3|8|15, 3)
+        also "f_rest", the SH coefficients above the DC row rotated by the same R (register.py:85, differentiable in r)."""
         from .render import build_cov3D
         R = rot6d_to_rotmat(self.r)
         q_R = rotmat_to_quat(R)
@@ -189,7 +194,11 @@ class Register(nn.Module):
         rot = F.normalize(quaternion_multiply(F.normalize(rotations.detach(), dim=-1), q_R[None]), p=2, dim=-1)
         pts = pts + self.t[None]
         cov = build_cov3D(torch.exp(ls), rot, scaling_modifier)
-        return {"points": pts, "scales": ls, "rotations": rot, "cov3D": cov, "origin": origin}
+        out = {"points": pts, "scales": ls, "rotations": rot, "cov3D": cov, "origin": origin}
+        if f_rest is not None:
+            from .render.transform_utils import rotate_shs_torch
+            out["f_rest"] = rotate_shs_torch(f_rest.detach(), R)
+        return out
 
 
 def pack_params(register: Register, origin: Tensor):
@@ -259,6 +268,12 @@ class NativeRegistration(object):
         else:
             self.sh, self.cp = gaussians.get_features.detach().float().contiguous(), None
         sh_degree = gaussians.active_sh_degree
+        # sh_degree > 0: the coefficients above the DC row turn with the Gaussians; self.sh stays as loaded, the renders read
+        # self.sh_rot (written once per iteration)
+        self.rotate_sh = self.sh is not None and sh_degree > 0 and self.sh.shape[1] > 1
+        self.sh_rot = torch.empty_like(self.sh) if self.rotate_sh else None
+        rest = gaussians._features_rest
+        self.f_rest = rest.detach().float().contiguous() if sh_degree > 0 and rest.dim() == 3 and rest.shape[1] > 0 else None
         self.cams: List[RasterCamera] = [get_rasterizer(c, sh_degree, False, background)._cam for c in cameras]
         self.gts = [g.detach().to(dev).float().contiguous() for g in gts]
         self.lam = float(lambda_ssim)
@@ -268,6 +283,7 @@ class NativeRegistration(object):
         self.loss_hist = torch.zeros(max(int(num_iter), 1), dtype=torch.float32, device=dev)
         self.dparams = torch.zeros(17, dtype=torch.float32, device=dev)
         self.ws_reg = torch.empty(int(lib.nm_regist_bwd_workspace(self.K)), dtype=torch.uint8, device=dev)
+        self.ws_shrot = torch.empty(int(lib.nm_sh_rotate_bwd_workspace(self.K)), dtype=torch.uint8, device=dev) if self.rotate_sh else None
         self.ws_ssim = {}
         self.n = 0
         self.last_renders: List[Tensor] = []
@@ -291,8 +307,11 @@ class NativeRegistration(object):
         means3D, cov6 = regist_apply(self.xyz, self.ls, self.rot, params, self.mod)
         self.dparams.zero_()
         self.last_renders = []
+        sh = self.sh
+        if self.rotate_sh:
+            sh = self._rotated_sh(params)
         for cam, gt in zip(self.cams, self.gts):
-            color, _, rec = raster_forward_raw(cam, means3D, self.sh, self.cp, self.op, cov6)
+            color, _, rec = raster_forward_raw(cam, means3D, sh, self.cp, self.op, cov6)
             h, w = int(color.shape[-2]), int(color.shape[-1])
             gimg = torch.empty_like(color)
             L.check(lib.nm_pixel_loss(self.kind, 1.0 - self.lam, h, w, 0, 0, L.ptr(color), L.ptr(gt), L.ptr(loss), L.ptr(gimg), stream),
@@ -301,8 +320,12 @@ class NativeRegistration(object):
                 ws = self._ssim_ws(h, w)
                 L.check(lib.nm_ssim_loss(self.lam, h, w, L.ptr(color), L.ptr(gt), L.ptr(loss), L.ptr(gimg), L.ptr(ws), ws.numel(), stream),
                         "nm_ssim_loss")
-            dm, _, dcov, _, _, _ = raster_backward_raw(rec, gimg, need_cov=True)
+            dm, _, dcov, _, dsh, _ = raster_backward_raw(rec, gimg, need_cov=True, need_color=self.rotate_sh)
             regist_backward(self.xyz, self.ls, self.rot, params, self.mod, dm, dcov, self.dparams, self.ws_reg)
+            if self.rotate_sh:                                            # dparams[0:9] (dR) += the colours' share
+                L.check(lib.nm_sh_rotate_backward(self.K, self.sh.shape[1], 1, L.ptr(params), L.ptr(self.sh), L.ptr(dsh),
+                                                  L.ptr(self.dparams), None, L.ptr(self.ws_shrot), self.ws_shrot.numel(), stream),
+                        "nm_sh_rotate_backward")
             if keep_renders:
                 self.last_renders.append(color)
         params_backward(reg, R, q_R, self.dparams)
@@ -312,15 +335,26 @@ class NativeRegistration(object):
         reg.scheduler.step()
         self.n += 1
 
+    def _rotated_sh(self, params: Tensor) -> Tensor:
+        """self.sh_rot <- diag(1, D(R)) self.sh with R = params[0:9], on the device (nothing is read back)."""
+        L.check(L.lib().nm_sh_rotate(self.K, self.sh.shape[1], 1, L.ptr(params), L.ptr(self.sh), L.ptr(self.sh_rot),
+                                     L.stream_ptr(self.dev)), "nm_sh_rotate")
+        return self.sh_rot
+
     def losses(self) -> np.ndarray:
         return self.loss_hist[:self.n].double().cpu().numpy()
 
-    def transformed(self):
+    def transformed(self, with_f_rest: bool = False):
         """(means3D, log-scales, rotations) under the transform the LAST iteration rendered with (regist.py:204 saves the
-        Gaussians of the last forward pass, i.e. one optimizer step behind registered_params.npz), through nm_regist_apply."""
+        Gaussians of the last forward pass, i.e. one optimizer step behind registered_params.npz), through nm_regist_apply.
+        with_f_rest: a fourth entry, the SH coefficients above the DC row under the same transform through nm_sh_rotate (None
+        at sh_degree 0)."""
         params = self.last_params if self.last_params is not None else pack_params(self.reg, self.origin)[2]
         m, _, ls, rq = regist_apply(self.xyz, self.ls, self.rot, params, self.mod, want_params=True)
-        return m, ls, rq
+        if not with_f_rest:
+            return m, ls, rq
+        from .render.transform_utils import sh_rotate
+        return m, ls, rq, (sh_rotate(self.f_rest, params[0:9], False) if self.f_rest is not None else None)
 
 
 def ema_of(losses) -> float:
@@ -339,7 +373,10 @@ def regist_step_torch(register: Register, gaussians, cameras: Sequence, gts: Seq
     from .render import get_rasterizer
     from .tune import l1_loss, l2_loss, ssim
     pix = {"l1": l1_loss, "l2": l2_loss}[pixel_loss]
-    pack = register(gaussians._xyz, gaussians._scaling, gaussians._rotation, scaling_modifier)
+    rotate_sh = (not force_mask_data) and gaussians.active_sh_degree > 0 and gaussians._features_rest.shape[1] > 0
+    pack = register(gaussians._xyz, gaussians._scaling, gaussians._rotation, scaling_modifier,
+                    f_rest=gaussians._features_rest if rotate_sh else None)
+    shs = torch.cat((gaussians._features_dc.detach(), pack["f_rest"]), dim=1) if rotate_sh else gaussians.get_features.detach()
     op = gaussians.get_opacity.detach()
     K = pack["points"].shape[0]
     loss = 0.0
@@ -351,7 +388,7 @@ def regist_step_torch(register: Register, gaussians, cameras: Sequence, gts: Seq
             img, _ = rast(means3D=pack["points"], means2D=means2D, opacities=op, shs=None,
                           colors_precomp=torch.ones(K, 3, device=op.device), cov3D_precomp=pack["cov3D"])
         else:
-            img, _ = rast(means3D=pack["points"], means2D=means2D, opacities=op, shs=gaussians.get_features.detach(),
+            img, _ = rast(means3D=pack["points"], means2D=means2D, opacities=op, shs=shs,
                           colors_precomp=None, cov3D_precomp=pack["cov3D"])
         gt = gt.to(img.device)
         loss = loss + (1.0 - lambda_ssim) * pix(img, gt)
@@ -424,9 +461,10 @@ def regist_gaussians(cfg, log=print) -> Optional[float]:
     background = torch.tensor([1.0, 1.0, 1.0] if cfg.video_data.data.get("white_background", False) else [0.0, 0.0, 0.0],
                               dtype=torch.float32, device=device)
     gaussians = nio.load_gaussians_ply(cfg.gaussian.kernels_path, cfg.gaussian.sh_degree, device=device)
-    if cfg.gaussian.sh_degree > 0 and gaussians._features_rest.numel() > 0:
-        raise NotImplementedError("registration of Gaussians with sh_degree > 0: rotating the SH coefficients "
-                                  "(transform_shs_by_quat) needs e3nn's Wigner matrices and is not provided")
+    rotate_sh = cfg.gaussian.sh_degree > 0 and gaussians._features_rest.numel() > 0
+    if rotate_sh and not bool(cfg.register.get("rotate_sh", False)):
+        raise NotImplementedError("registration of Gaussians with sh_degree > 0 rotates the SH coefficients with the Gaussians "
+                                  "(transform_shs_by_quat); it is opt-in: set `register.rotate_sh: true` in the config")
     save_config(cfg, data_root / "config.yaml")
     debug_root = data_root / "debug"
     if debug:
@@ -465,8 +503,9 @@ def regist_gaussians(cfg, log=print) -> Optional[float]:
     np.savez_compressed(data_root / "registered_params.npz", r=register.get_rotmat.detach().cpu().numpy(),
                         t=register.t.detach().cpu().numpy(), s=register.s.detach().cpu().numpy(), o=run.origin.cpu().numpy())
     with torch.no_grad():
-        m, ls, rq = run.transformed()
-    gaussians.set_params(m, gaussians._features_dc, gaussians._features_rest, ls, rq, gaussians._opacity)
+        m, ls, rq, f_rest = run.transformed(with_f_rest=True)
+    gaussians.set_params(m, gaussians._features_dc, f_rest if f_rest is not None else gaussians._features_rest, ls, rq,
+                         gaussians._opacity)
     nio.save_gaussians_ply(gaussians, data_root / "registered_kernels.ply")
     log(f"\nRegistration finished. Loss: {ema:.7f}")
     log("===================================")

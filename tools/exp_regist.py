@@ -2,13 +2,15 @@
 """Registration loop timing (python -m neuma_amd.regist): the native iteration (nm_regist_apply, 3 x render forward + pixel loss
 + nm_ssim_loss + render adjoint + nm_regist_backward, RAdam on 10 scalars) against the torch autograd path (Register.forward +
 build_cov3D + GaussianRasterizer + tune.ssim) on a synthetic scene of the `burger` configuration (200k Gaussians, 3 views,
-1920x1080, sh 0) from synth.py, ground truth rendered at a known transform.
+1920x1080, sh 0) from synth.py, ground truth rendered at a known transform.  --sh DEG: the same scene with SH colours of that
+degree, rotated with the Gaussians every iteration (nm_sh_rotate / nm_sh_rotate_backward; the targets too).
 
-    python tools/exp_regist.py [--iters 200] [--warmup 20] [--lam 0.1] [--mask] [--only native|torch]
+    python tools/exp_regist.py [--iters 200] [--warmup 20] [--lam 0.1] [--mask] [--only native|torch] [--sh 0..3]
 
 prints one JSON line: iterations/s of both paths.  Per-launch kernel times come from a run of its own:
     rocprofv3 --kernel-trace --stats -d <dir> -o regist -- python tools/exp_regist.py --only native --iters 50
-(k_regist_apply, k_regist_bwd + k_regist_reduce, k_ssim_fwd + k_ssim_bwd in the stats CSV)."""
+(k_regist_apply, k_regist_bwd + k_regist_reduce, k_ssim_fwd + k_ssim_bwd, with --sh 1..3 k_sh_rotate, k_sh_rotate_bwd +
+k_sh_rotate_finish in the stats CSV)."""
 import argparse
 import json
 import math
@@ -21,10 +23,10 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch  # noqa: E402
 
 
-def scene(dev, K, W, H, V):
+def scene(dev, K, W, H, V, sh=0):
     from neuma_amd import synth
     from neuma_amd.render.gaussian_model import GaussianModel
-    sc = synth.make_scene("burger", override=dict(K=K, W=W, H=H, V=V))
+    sc = synth.make_scene("burger", override=dict(K=K, W=W, H=H, V=V, sh=sh))
     gm = GaussianModel(sc.cfg["sh"])
     sh = torch.tensor(sc.g_sh, device=dev)
     gm.set_params(torch.tensor(sc.g_xyz, device=dev), sh[:, :1].contiguous(), sh[:, 1:].contiguous(), torch.tensor(sc.g_logscale, device=dev),
@@ -43,11 +45,12 @@ def main():
     ap.add_argument("--W", type=int, default=1920)
     ap.add_argument("--H", type=int, default=1080)
     ap.add_argument("--V", type=int, default=3)
+    ap.add_argument("--sh", type=int, default=0, choices=[0, 1, 2, 3], help="SH degree of the scene's colours")
     a = ap.parse_args()
     from neuma_amd.regist import NativeRegistration, Register, euler_to_quat, pack_params, quat_to_rot6d, regist_apply, regist_step_torch
     from neuma_amd.render import flush_pending, raster_forward_raw
     dev = torch.device("cuda", 0)
-    gm, cams = scene(dev, a.K, a.W, a.H, a.V)
+    gm, cams = scene(dev, a.K, a.W, a.H, a.V, a.sh)
     bg = torch.zeros(3, device=dev)
     sched = dict(max_steps=20000, learning_rate_alpha=0.01)
     cfg = dict(INIT_R=[0.0, 0.0, 0.0], INIT_T=[0.0, 0.0, 0.0], INIT_S=[1.0], lr_r=1e-4, lr_t=5e-5, lr_s=1e-5, scheduler=sched)
@@ -57,9 +60,10 @@ def main():
     with torch.no_grad():
         _, _, params = pack_params(truth, probe.origin)
         m, c6 = regist_apply(probe.xyz, probe.ls, probe.rot, params)
-        gts = [raster_forward_raw(cam, m, probe.sh, probe.cp, probe.op, c6)[0].clone() for cam in probe.cams]
+        sh = probe._rotated_sh(params) if probe.rotate_sh else probe.sh
+        gts = [raster_forward_raw(cam, m, sh, probe.cp, probe.op, c6)[0].clone() for cam in probe.cams]
     flush_pending()
-    out = {"K": a.K, "W": a.W, "H": a.H, "views": a.V, "lambda_ssim": a.lam, "mask": a.mask, "iters": a.iters}
+    out = {"K": a.K, "W": a.W, "H": a.H, "views": a.V, "lambda_ssim": a.lam, "mask": a.mask, "iters": a.iters, "sh": a.sh}
     if a.only in (None, "native"):
         reg = Register(cfg, device=dev)
         reg.training_setup()
