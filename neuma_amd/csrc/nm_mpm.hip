@@ -5,15 +5,15 @@
 //   * the grid lives in HBM as 4x4x4-node blocks of float4 {mv.xyz, m} / {v.xyz, -} (1 KiB per block),
 //     and only blocks touched by a particle stencil are ever cleared or updated (active-block list built
 //     by p2g with an epoch flag per block) — the reference sweeps all G^3 cells 12 times per step;
-//   * scatters (p2g, g2p-adjoint) accumulate in a per-wave LDS tile covering the bounding box of the wave's
-//     particles and flush each touched node once with global atomics.  ds_add_f32 is NOT used: measured on
-//     MI355X it retires ~0.33 lanes/clk/CU (tools/ubench_atomics.hip), 20x slower than a plain LDS
-//     read-modify-write.  Instead a workgroup is ONE wave that owns its tile; for a fixed stencil offset two
-//     lanes collide only if they share a base cell, so lanes elect one owner per base cell (LDS ticket) and
-//     the owners do plain ds_read_b128 / add / ds_write_b128; losers retry in the next round.  Lanes take
-//     particles with stride PB, so cell-sorted inputs give ~1 round.  A wave whose particles are too spread
-//     out falls back to direct global atomics: particle order affects speed only, never results beyond
-//     fp32 summation order;
+//   * scatters (p2g, g2p-adjoint) give every thread of a 256-thread workgroup one particle, accumulate in an LDS tile that
+//     covers the bounding box of the workgroup's stencil origins and flush each touched node once with global atomics.
+//     ds_add_f32 is NOT used: measured on MI355X it retires ~0.33 lanes/clk/CU (tools/ubench_atomics.hip), 20x slower than
+//     a plain LDS read-modify-write.  Two modes (MpmK.smode): "f64", the default, adds every contribution with ds_add_f64
+//     into fp64 planes of the tile (wg_scatter_f64); "sort" counting-sorts the particles by origin cell in LDS, sums each
+//     cell's members and pushes the cell sums into a float4 tile one stencil offset at a time, between barriers
+//     (wg_scatter).  A chunk whose box exceeds the tile is cut into groups at the jumps of the particle order (f64), or is
+//     axis-compressed or handed to per-wave 8x8x8 boxes (sort, wave_scatter); what still does not fit goes to per-particle
+//     global atomics: particle order affects speed only, never results beyond fp32 summation order;
 //   * stencil nodes with an index >= G (reference: out-of-bounds access when x > 1-1.5dx) land in
 //     padding blocks whose velocity is defined as zero.
 #include "nm_common.h"
