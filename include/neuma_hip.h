@@ -535,6 +535,19 @@ int nm_regist_backward(int32_t k, const float* xyz, const float* log_scales, con
                        float scale_modifier, const float* dL_dmeans3D, const float* dL_dcov6, float* dL_dparams,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* The activations of a 3DGS parameter set (gaussian_model.py:26-41), one pass over K Gaussians: log_scales (K,3), rot (K,4)
+ * raw (normalised here, 16-byte aligned), opacity_logit (K,1).
+ *   cov6    = strip_symmetric(L L^T), L = build_rotation(normalize(rot)) diag(scale_modifier exp(log_scales))
+ *   opacity = sigmoid(opacity_logit)
+ * Either output may be NULL (its inputs may then be NULL too). */
+int nm_gaussian_activate(int32_t k, const float* log_scales, const float* rot, const float* opacity_logit,
+                         float scale_modifier, float* cov6, float* opacity, void* stream);
+/* Its adjoint per Gaussian: dL_dlog_scales (K,3), dL_drot (K,4, through the normalisation) from dL_dcov6 (K,6), and
+ * dL_dopacity_logit (K,1) from dL_dopacity (K,1).  Outputs are overwritten, not accumulated; any of them may be NULL. */
+int nm_gaussian_activate_backward(int32_t k, const float* log_scales, const float* rot, const float* opacity_logit,
+                                  float scale_modifier, const float* dL_dcov6, const float* dL_dopacity,
+                                  float* dL_dlog_scales, float* dL_drot, float* dL_dopacity_logit, void* stream);
+
 /* SH colour coefficients rotated with the Gaussians (transform_shs_by_rotmat, modules/d3gs/utils/transform_utils.py:41-104):
  * shs_out[g, :, ch] = diag(1, D_1, D_2, D_3)(R) shs_in[g, :, ch], D defined by sum_j c'_j Y_j(R d) = sum_j c_j Y_j(d) for
  * the rasterizer's basis Y, built from R as a polynomial (sh_rotation_matrices of render/transform_utils.py is the same
@@ -588,6 +601,26 @@ int nm_image_metrics(int32_t b, int32_t c, int32_t h, int32_t w, const float* pr
 size_t nm_nn_workspace(int32_t b, int32_t n_query, int32_t n_target);
 int nm_nearest_neighbors(int32_t b, int32_t n_query, int32_t n_target, const float* query, const float* target,
                          int64_t* idx_out, double* d2_out, void* workspace, size_t workspace_bytes, void* stream);
+/* Exact k-nearest-neighbour search, 1 <= k <= 16, with the clouds, the binning and the distance arithmetic of
+ * nm_nearest_neighbors: for every query the k targets with the smallest (distance^2, target index) in lexicographic order,
+ * ascending.  idx_out (b, n_query, k) (DEVICE, int64); d2_out (b, n_query, k) (DEVICE, fp64) or NULL.  With k = 1 the result
+ * equals nm_nearest_neighbors bit for bit.  exclude_same_index != 0 (query and target are the same cloud): target i is no
+ * neighbour of query i - dropped by index, not by distance, so a coincident duplicate stays a neighbour at distance 0.  A query
+ * with a NaN / Inf coordinate gets indices 0 and distances NaN (as does a slot for which no finite target is left).  The k best
+ * are held in registers per thread; the walk stops once the k-th best squared distance is at most the squared distance to the
+ * slab beyond each face of the visited block of cells.  No atomics on floating-point values, no host synchronisation: two calls
+ * give identical bits.  workspace: nm_knn_workspace(b, n_query, n_target, k) bytes (0 = invalid sizes).  k out of range, fewer
+ * than k eligible targets (n_target, less one with exclude_same_index) or a too small workspace -> -1 before any device work. */
+size_t nm_knn_workspace(int32_t b, int32_t n_query, int32_t n_target, int32_t k);
+int nm_knn(int32_t b, int32_t n_query, int32_t n_target, int32_t k, int32_t exclude_same_index, const float* query,
+           const float* target, int64_t* idx_out, double* d2_out, void* workspace, size_t workspace_bytes, void* stream);
+/* out[i] (DEVICE, fp32) = the mean of the k smallest squared distances from points[i] to the OTHER points of the cloud
+ * (n, 3), excluded by index; the k fp64 distances are summed ascending in fp64 and the mean is rounded once.  k = 3 is the
+ * documented behaviour of simple_knn's distCUDA2 (3DGS scale initialisation).  n - 1 < k -> -1.  workspace:
+ * nm_knn_mean_dist2_workspace(n) bytes. */
+size_t nm_knn_mean_dist2_workspace(int32_t n);
+int nm_knn_mean_dist2(int32_t n, const float* points, int32_t k, float* out, void* workspace, size_t workspace_bytes,
+                      void* stream);
 /* Both directions of a Chamfer distance (metrics.py chamfer_distance_kdtree) in one call: p1 (b, n1, 3), p2 (b, n2, 3).
  * cd12_out[b] / cd21_out[b] (DEVICE, fp64) = the mean over p1 (p2) of the squared distance to its nearest point of p2 (p1),
  * fixed-order sums; NaN for an item where either cloud holds a NaN / Inf coordinate (other items are unaffected).

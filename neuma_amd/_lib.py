@@ -137,6 +137,8 @@ SIGNATURES = {
     "nm_regist_apply": (C.c_int, [_I32, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P]),
     "nm_regist_bwd_workspace": (_SZ, [_I32]),
     "nm_regist_backward": (C.c_int, [_I32, _P, _P, _P, _P, _F, _P, _P, _P, _P, _SZ, _P]),
+    "nm_gaussian_activate": (C.c_int, [_I32, _P, _P, _P, _F, _P, _P, _P]),
+    "nm_gaussian_activate_backward": (C.c_int, [_I32, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P]),
     "nm_sh_rotate": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P]),
     "nm_sh_rotate_bwd_workspace": (_SZ, [_I32]),
     "nm_sh_rotate_backward": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P]),
@@ -146,6 +148,10 @@ SIGNATURES = {
     "nm_image_metrics": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _SZ, _P]),
     "nm_nn_workspace": (_SZ, [_I32, _I32, _I32]),
     "nm_nearest_neighbors": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
+    "nm_knn_workspace": (_SZ, [_I32, _I32, _I32, _I32]),
+    "nm_knn": (C.c_int, [_I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
+    "nm_knn_mean_dist2_workspace": (_SZ, [_I32]),
+    "nm_knn_mean_dist2": (C.c_int, [_I32, _P, _I32, _P, _P, _SZ, _P]),
     "nm_chamfer_workspace": (_SZ, [_I32, _I32, _I32]),
     "nm_chamfer": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "nm_mesh_inside_workspace": (_SZ, [_I32, _I32]),

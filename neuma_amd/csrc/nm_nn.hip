@@ -1,4 +1,4 @@
-// Exact 1-nearest-neighbour search between point clouds, batched over B pairs, and the Chamfer distance of
+// Exact 1- and k-nearest-neighbour search between point clouds, batched over B pairs, and the Chamfer distance of
 // modules/tune/metrics.py (chamfer_distance_kdtree: one scipy cKDTree per batch item on the host) on the device.
 //
 // Each cloud is binned once, per batch item, into a uniform grid over its own bounding box:
@@ -15,6 +15,8 @@
 // Distances are fp64 from the fp32 coordinates, the winner is the lexicographic minimum of (distance^2, target index), so the
 // result does not depend on the order of points inside a cell (nor on the atomics' ranks).  The per-item means are fixed-order
 // fp64 sums over the queries in their ORIGINAL order (k_nn_mean_part, k_nn_mean_finish): two calls give identical bits.
+// The k-NN search (k_nn_search_k, 1 <= k <= 16: nm_knn, and nm_knn_mean_dist2 = simple_knn's distCUDA2 at k = 3) is the same
+// walk with a k-best list per thread in registers; it stops on the k-th best instead of the best.
 #include "nm_common.h"
 
 #include <rocprim/rocprim.hpp>
@@ -226,19 +228,62 @@ __global__ void __launch_bounds__(kNnThreads) k_nn_scatter(int P, int cmax, cons
   sorted[pos] = make_float4(pts[3 * gi], pts[3 * gi + 1], pts[3 * gi + 2], __int_as_float(i));
 }
 
-// squared distance in fp64, summed x, y, z without contraction (cKDTree's order)
+// squared distance in fp64, summed x, y, z without contraction (cKDTree's order).  The pragma is what keeps the three products
+// and the two sums separately rounded: HIP's __dmul_rn / __dadd_rn are plain * and + in a header, and the compiler fuses them
+// into fmas under its default contraction.
 __device__ __forceinline__ double nn_d2(double qx, double qy, double qz, const float4& t) {
+#pragma clang fp contract(off)
   const double dx = qx - (double)t.x, dy = qy - (double)t.y, dz = qz - (double)t.z;
-  return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+  return (dx * dx + dy * dy) + dz * dz;
 }
 
-__device__ __forceinline__ void nn_scan_range(const float4* __restrict__ T, int s, int e, double qx, double qy, double qz, double& best,
-                                              int& bi) {
+// What a search keeps per query: visit() offers one target, bound() is the squared distance beyond which no target can
+// enter any more (the best for 1-NN, the k-th best for k-NN).
+struct NnOne {
+  double best = INFINITY;
+  int bi = INT_MAX;
+  __device__ __forceinline__ void visit(double d, int j) {
+    if (d < best || (d == best && j < bi)) { best = d; bi = j; }
+  }
+  __device__ __forceinline__ double bound() const { return best; }
+};
+
+// The k best (distance^2, index) pairs in ascending lexicographic order, held in the LAST k of CAP >= k register slots: the
+// first CAP - k slots hold (-inf, -1) sentinels that nothing ever moves, so the k-th best is always slot CAP - 1 and no slot is
+// ever indexed by a run-time value.  Every loop over the slots is fully unrolled; the insertion is a compare-and-shift over all
+// of them.
+template <int CAP>
+struct NnK {
+  double d[CAP];
+  int j[CAP];
+  int skip;             // the target index that is no neighbour (exclude_same_index), -1 for none
+  __device__ __forceinline__ NnK(int k, int skip_) : skip(skip_) {
+#pragma unroll
+    for (int s = 0; s < CAP; ++s) {
+      d[s] = s < CAP - k ? -INFINITY : INFINITY;
+      j[s] = s < CAP - k ? -1 : INT_MAX;
+    }
+  }
+  __device__ __forceinline__ static bool less(double da, int ja, double db, int jb) { return da < db || (da == db && ja < jb); }
+  __device__ __forceinline__ void visit(double dd, int jj) {
+    if (jj == skip || !less(dd, jj, d[CAP - 1], j[CAP - 1])) return;
+#pragma unroll
+    for (int s = CAP - 1; s > 0; --s) {
+      const bool before = less(dd, jj, d[s - 1], j[s - 1]);      // the newcomer goes in front of slot s - 1: slot s takes that one
+      const bool here = !before && less(dd, jj, d[s], j[s]);
+      d[s] = before ? d[s - 1] : (here ? dd : d[s]);
+      j[s] = before ? j[s - 1] : (here ? jj : j[s]);
+    }
+    if (less(dd, jj, d[0], j[0])) { d[0] = dd; j[0] = jj; }
+  }
+  __device__ __forceinline__ double bound() const { return d[CAP - 1]; }
+};
+
+template <class Acc>
+__device__ __forceinline__ void nn_scan_range(const float4* __restrict__ T, int s, int e, double qx, double qy, double qz, Acc& acc) {
   for (int k = s; k < e; ++k) {
     const float4 t = T[k];
-    const double d = nn_d2(qx, qy, qz, t);
-    const int j = __float_as_int(t.w);
-    if (d < best || (d == best && j < bi)) { best = d; bi = j; }
+    acc.visit(nn_d2(qx, qy, qz, t), __float_as_int(t.w));
   }
 }
 
@@ -246,6 +291,58 @@ __device__ __forceinline__ void nn_scan_range(const float4* __restrict__ T, int 
 __device__ __forceinline__ double nn_out2(double q, double lo, double hi, double s) {
   const double g = q < lo - s ? (lo - s) - q : (q > hi + s ? q - (hi + s) : 0.0);
   return g * g;
+}
+
+// The shell walk of one finite query over the targets' grid: growing shells of cells around the query's own (clamped) cell until
+// acc.bound() is at most the lower bound on the squared distance to every unvisited cell, max(n) shells at the most.
+template <class Acc>
+__device__ __forceinline__ void nn_walk(const float4& q, const NnGrid& G, const int* __restrict__ S, const float4* __restrict__ tsorted,
+                                        Acc& acc) {
+  const double qv[3] = {(double)q.x, (double)q.y, (double)q.z};
+  const int n0 = G.n[0], n1 = G.n[1], n2 = G.n[2];
+  int c[3];
+  double out2[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    c[k] = nn_cell(qv[k], G.o[k], G.inv_h[k], G.n[k]);
+    out2[k] = nn_out2(qv[k], G.o[k], G.hi[k], G.slack[k]);
+  }
+  const int rmax = max(n0, max(n1, n2));
+  for (int r = 0; r < rmax; ++r) {
+    int lo[3], hi[3], plo[3], phi[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      lo[k] = max(c[k] - r, 0); hi[k] = min(c[k] + r, G.n[k] - 1);
+      plo[k] = max(c[k] - r + 1, 0); phi[k] = min(c[k] + r - 1, G.n[k] - 1);   // the block of shell r - 1 (empty at r = 0)
+    }
+    for (int x = lo[0]; x <= hi[0]; ++x) {
+      const bool xin = r > 0 && x >= plo[0] && x <= phi[0];
+      for (int y = lo[1]; y <= hi[1]; ++y) {
+        const int base = (x * n1 + y) * n2;       // the cells of one (x, y) column are contiguous in the sorted cloud
+        if (!(xin && y >= plo[1] && y <= phi[1])) {
+          nn_scan_range(tsorted, S[base + lo[2]], S[base + hi[2] + 1], qv[0], qv[1], qv[2], acc);
+        } else {
+          if (lo[2] < plo[2]) nn_scan_range(tsorted, S[base + lo[2]], S[base + lo[2] + 1], qv[0], qv[1], qv[2], acc);
+          if (hi[2] > phi[2]) nn_scan_range(tsorted, S[base + hi[2]], S[base + hi[2] + 1], qv[0], qv[1], qv[2], acc);
+        }
+      }
+    }
+    // lower bound on the squared distance to every unvisited cell: such a cell lies beyond one face of the block, inside the box
+    double lb2 = INFINITY;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const double side = out2[(k + 1) % 3] + out2[(k + 2) % 3];
+      if (lo[k] > 0) {
+        const double g = fmax(qv[k] - (G.o[k] + lo[k] * G.h[k]) - G.slack[k], 0.0);
+        lb2 = fmin(lb2, g * g + side);
+      }
+      if (hi[k] < G.n[k] - 1) {
+        const double g = fmax((G.o[k] + (hi[k] + 1) * G.h[k]) - G.slack[k] - qv[k], 0.0);
+        lb2 = fmin(lb2, g * g + side);
+      }
+    }
+    if (acc.bound() <= lb2) break;
+  }
 }
 
 // grid (ceil(N / 256), B): thread t takes the t-th query of the query cloud's cell order of item blockIdx.y
@@ -258,60 +355,41 @@ __global__ void __launch_bounds__(kNnThreads) k_nn_search(int N, int cmax_t, con
   const int item = blockIdx.y;
   const float4 q = qsorted[(size_t)item * N + t];
   const int qi = __float_as_int(q.w);
-  const NnGrid& G = tgrid[item];
-  const int* S = tstart + (size_t)item * cmax_t;
-  double best = INFINITY;
-  int bi = INT_MAX;
-  if (nn_finite3(q.x, q.y, q.z)) {
-    const double qv[3] = {(double)q.x, (double)q.y, (double)q.z};
-    const int n0 = G.n[0], n1 = G.n[1], n2 = G.n[2];
-    int c[3];
-    double out2[3];
+  NnOne acc;
+  if (nn_finite3(q.x, q.y, q.z)) nn_walk(q, tgrid[item], tstart + (size_t)item * cmax_t, tsorted, acc);
+  const size_t o = (size_t)item * N + qi;
+  idx_out[o] = acc.bi == INT_MAX ? 0 : (int64_t)acc.bi;
+  if (d2_out) d2_out[o] = acc.bi == INT_MAX ? (double)NAN : acc.best;
+}
+
+// The same walk with a k-best list.  idx_out / d2_out (B, N, k), either may be NULL; mean_out (B, N) fp32 or NULL: the mean of
+// the k squared distances, summed ascending in fp64 and rounded once.  A slot that found no target: index 0, distance NaN.
+template <int CAP>
+__global__ void __launch_bounds__(kNnThreads) k_nn_search_k(int N, int cmax_t, int k, int exclude_same, const float4* __restrict__ qsorted,
+                                                            const NnGrid* __restrict__ tgrid, const int* __restrict__ tstart,
+                                                            const float4* __restrict__ tsorted, int64_t* __restrict__ idx_out,
+                                                            double* __restrict__ d2_out, float* __restrict__ mean_out) {
+  const int t = blockIdx.x * kNnThreads + threadIdx.x;
+  if (t >= N) return;
+  const int item = blockIdx.y;
+  const float4 q = qsorted[(size_t)item * N + t];
+  const int qi = __float_as_int(q.w);
+  NnK<CAP> acc(k, exclude_same ? qi : -1);
+  if (nn_finite3(q.x, q.y, q.z)) nn_walk(q, tgrid[item], tstart + (size_t)item * cmax_t, tsorted, acc);
+  const size_t row = (size_t)item * N + qi;
+  const int off = CAP - k;                                  // slot s holds neighbour s - off
+  double sum = 0.0;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      c[k] = nn_cell(qv[k], G.o[k], G.inv_h[k], G.n[k]);
-      out2[k] = nn_out2(qv[k], G.o[k], G.hi[k], G.slack[k]);
-    }
-    const int rmax = max(n0, max(n1, n2));
-    for (int r = 0; r < rmax; ++r) {
-      int lo[3], hi[3], plo[3], phi[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        lo[k] = max(c[k] - r, 0); hi[k] = min(c[k] + r, G.n[k] - 1);
-        plo[k] = max(c[k] - r + 1, 0); phi[k] = min(c[k] + r - 1, G.n[k] - 1);   // the block of shell r - 1 (empty at r = 0)
-      }
-      for (int x = lo[0]; x <= hi[0]; ++x) {
-        const bool xin = r > 0 && x >= plo[0] && x <= phi[0];
-        for (int y = lo[1]; y <= hi[1]; ++y) {
-          const int base = (x * n1 + y) * n2;       // the cells of one (x, y) column are contiguous in the sorted cloud
-          if (!(xin && y >= plo[1] && y <= phi[1])) {
-            nn_scan_range(tsorted, S[base + lo[2]], S[base + hi[2] + 1], qv[0], qv[1], qv[2], best, bi);
-          } else {
-            if (lo[2] < plo[2]) nn_scan_range(tsorted, S[base + lo[2]], S[base + lo[2] + 1], qv[0], qv[1], qv[2], best, bi);
-            if (hi[2] > phi[2]) nn_scan_range(tsorted, S[base + hi[2]], S[base + hi[2] + 1], qv[0], qv[1], qv[2], best, bi);
-          }
-        }
-      }
-      // lower bound on the squared distance to every unvisited cell: such a cell lies beyond one face of the block, inside the box
-      double lb2 = INFINITY;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const double side = out2[(k + 1) % 3] + out2[(k + 2) % 3];
-        if (lo[k] > 0) {
-          const double g = fmax(qv[k] - (G.o[k] + lo[k] * G.h[k]) - G.slack[k], 0.0);
-          lb2 = fmin(lb2, g * g + side);
-        }
-        if (hi[k] < G.n[k] - 1) {
-          const double g = fmax((G.o[k] + (hi[k] + 1) * G.h[k]) - G.slack[k] - qv[k], 0.0);
-          lb2 = fmin(lb2, g * g + side);
-        }
-      }
-      if (best <= lb2) break;
+  for (int s = 0; s < CAP; ++s) {
+    if (s >= off) {
+      const bool found = acc.j[s] != INT_MAX;
+      const double d = found ? acc.d[s] : (double)NAN;
+      if (idx_out) idx_out[row * k + (s - off)] = found ? (int64_t)acc.j[s] : 0;
+      if (d2_out) d2_out[row * k + (s - off)] = d;
+      sum += d;
     }
   }
-  const size_t o = (size_t)item * N + qi;
-  idx_out[o] = bi == INT_MAX ? 0 : (int64_t)bi;
-  if (d2_out) d2_out[o] = bi == INT_MAX ? (double)NAN : best;
+  if (mean_out) mean_out[row] = (float)(sum / (double)k);
 }
 
 // grid (gmean, B): fixed-order partial sums of d2 over the queries in their original order
@@ -363,6 +441,24 @@ static int nn_bin(const NnBin& w, const float* pts, hipStream_t s) {
 static int nn_search(const NnBin& q, const NnBin& t, int64_t* idx, double* d2, hipStream_t s) {
   NM_LAUNCH(k_nn_search, dim3(nm_div_up(q.p, kNnThreads), q.b), dim3(kNnThreads), 0, s, q.p, t.cmax, (const float4*)q.sorted,
             (const NnGrid*)t.grid, (const int*)t.start, (const float4*)t.sorted, idx, d2);
+  NM_LAUNCH_CHECK();
+  return NM_OK;
+}
+
+constexpr int kKnnMax = 16;
+
+static int nn_search_k(const NnBin& q, const NnBin& t, int k, int exclude_same, int64_t* idx, double* d2, float* mean, hipStream_t s) {
+  const dim3 g(nm_div_up(q.p, kNnThreads), q.b), b(kNnThreads);
+  if (k <= 4) {
+    NM_LAUNCH(k_nn_search_k<4>, g, b, 0, s, q.p, t.cmax, k, exclude_same, (const float4*)q.sorted, (const NnGrid*)t.grid,
+              (const int*)t.start, (const float4*)t.sorted, idx, d2, mean);
+  } else if (k <= 8) {
+    NM_LAUNCH(k_nn_search_k<8>, g, b, 0, s, q.p, t.cmax, k, exclude_same, (const float4*)q.sorted, (const NnGrid*)t.grid,
+              (const int*)t.start, (const float4*)t.sorted, idx, d2, mean);
+  } else {
+    NM_LAUNCH(k_nn_search_k<16>, g, b, 0, s, q.p, t.cmax, k, exclude_same, (const float4*)q.sorted, (const NnGrid*)t.grid,
+              (const int*)t.start, (const float4*)t.sorted, idx, d2, mean);
+  }
   NM_LAUNCH_CHECK();
   return NM_OK;
 }
@@ -421,6 +517,48 @@ extern "C" int nm_nearest_neighbors(int32_t b, int32_t n_query, int32_t n_target
   if ((rc = nn_bin(q, query, s)) != NM_OK) return rc;
   if ((rc = nn_bin(t, target, s)) != NM_OK) return rc;
   return nn_search(q, t, idx_out, d2_out, s);
+}
+
+extern "C" size_t nm_knn_workspace(int32_t b, int32_t n_query, int32_t n_target, int32_t k) {
+  if (k < 1 || k > kKnnMax) return 0;
+  return nm_nn_workspace(b, n_query, n_target);
+}
+
+extern "C" int nm_knn(int32_t b, int32_t n_query, int32_t n_target, int32_t k, int32_t exclude_same_index, const float* query,
+                      const float* target, int64_t* idx_out, double* d2_out, void* ws, size_t ws_bytes, void* stream) {
+  NM_REQUIRE(k >= 1 && k <= kKnnMax, "k must be in [1, 16]");
+  NM_REQUIRE(b >= 1 && b <= 65535, "b must be in [1, 65535]");
+  NM_REQUIRE(n_query >= 1 && n_target >= 1, "empty point cloud");
+  NM_REQUIRE(nn_sizes_ok(b, n_query, n_target), "b * points above 2^31 - 1");
+  NM_REQUIRE((int64_t)b * n_query * k < INT32_MAX, "b * n_query * k above 2^31 - 1");
+  NM_REQUIRE(n_target - (exclude_same_index ? 1 : 0) >= k, "fewer than k eligible targets");
+  NM_REQUIRE(query && target && idx_out && ws, "null pointer");
+  NM_REQUIRE(ws_bytes >= nm_knn_workspace(b, n_query, n_target, k), "workspace too small (nm_knn_workspace)");
+  const hipStream_t s = (hipStream_t)stream;
+  const NnBin q = carve_bin((char*)ws, b, n_query);
+  const NnBin t = carve_bin((char*)ws + q.total, b, n_target);
+  int rc;
+  if ((rc = nn_bin(q, query, s)) != NM_OK) return rc;
+  if ((rc = nn_bin(t, target, s)) != NM_OK) return rc;
+  return nn_search_k(q, t, k, exclude_same_index ? 1 : 0, idx_out, d2_out, nullptr, s);
+}
+
+extern "C" size_t nm_knn_mean_dist2_workspace(int32_t n) {
+  if (!nn_sizes_ok(1, n, n)) return 0;
+  return carve_bin(nullptr, 1, n).total;
+}
+
+extern "C" int nm_knn_mean_dist2(int32_t n, const float* points, int32_t k, float* out, void* ws, size_t ws_bytes, void* stream) {
+  NM_REQUIRE(k >= 1 && k <= kKnnMax, "k must be in [1, 16]");
+  NM_REQUIRE(n >= 1 && nn_sizes_ok(1, n, n), "bad point count");
+  NM_REQUIRE(n - 1 >= k, "fewer than k other points");
+  NM_REQUIRE(points && out && ws, "null pointer");
+  NM_REQUIRE(ws_bytes >= nm_knn_mean_dist2_workspace(n), "workspace too small (nm_knn_mean_dist2_workspace)");
+  const hipStream_t s = (hipStream_t)stream;
+  const NnBin c = carve_bin((char*)ws, 1, n);           // the cloud is binned once: it is both the queries and the targets
+  int rc;
+  if ((rc = nn_bin(c, points, s)) != NM_OK) return rc;
+  return nn_search_k(c, c, k, 1, nullptr, nullptr, out, s);
 }
 
 extern "C" size_t nm_chamfer_workspace(int32_t b, int32_t n1, int32_t n2) {

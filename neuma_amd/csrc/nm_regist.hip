@@ -4,6 +4,7 @@
 //   nm_regist_backward  its adjoint; per-block fp64 partials, then one fixed-order block: bitwise reproducible, no atomics
 //   nm_ssim_loss        modules/d3gs/utils/loss_utils.py:26-66 fused with its adjoint (separable 11-tap passes over LDS tiles)
 #include "nm_common.h"
+#include "nm_gaussian.h"
 #include "nm_ssim.h"
 
 namespace {
@@ -34,22 +35,6 @@ __device__ __forceinline__ void qmul(const float* a, const float* b, float* m) {
   m[1] = x1 * w0 + y1 * z0 - z1 * y0 + w1 * x0;
   m[2] = -x1 * z0 + y1 * w0 + z1 * x0 + w1 * y0;
   m[3] = x1 * y0 - y1 * x0 + z1 * w0 + w1 * z0;
-}
-
-// F.normalize (eps 1e-12); returns the divisor
-__device__ __forceinline__ float qnormalize(const float* v, float* n) {
-  const float len = fmaxf(sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]), 1e-12f);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) n[i] = v[i] / len;
-  return len;
-}
-
-// build_rotation (general_utils.py:101-124) of an already normalised quaternion
-__device__ __forceinline__ void quat_rot(const float* q, float* M) {
-  const float r = q[0], x = q[1], y = q[2], z = q[3];
-  M[0] = 1.f - 2.f * (y * y + z * z); M[1] = 2.f * (x * y - r * z);       M[2] = 2.f * (x * z + r * y);
-  M[3] = 2.f * (x * y + r * z);       M[4] = 1.f - 2.f * (x * x + z * z); M[5] = 2.f * (y * z - r * x);
-  M[6] = 2.f * (x * z - r * y);       M[7] = 2.f * (y * z + r * x);       M[8] = 1.f - 2.f * (x * x + y * y);
 }
 
 // Everything the forward and the adjoint share for one Gaussian.
@@ -100,29 +85,12 @@ __global__ void __launch_bounds__(256) k_regist_apply(int K, const float* __rest
 #pragma unroll
   for (int a = 0; a < 3; ++a)
     means3D[3 * i + a] = P.R[3 * a + 0] * f.d[0] + P.R[3 * a + 1] * f.d[1] + P.R[3 * a + 2] * f.d[2] + P.t[a];
-  float Lm[9];
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int b = 0; b < 3; ++b) Lm[3 * a + b] = f.M[3 * a + b] * f.e[b];
-  const int idx[6][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
-#pragma unroll
-  for (int c = 0; c < 6; ++c) {
-    const int a = idx[c][0], b = idx[c][1];
-    cov6[6 * i + c] = Lm[3 * a] * Lm[3 * b] + Lm[3 * a + 1] * Lm[3 * b + 1] + Lm[3 * a + 2] * Lm[3 * b + 2];
-  }
+  cov6_build(f.M, f.e, cov6, i);
   if (out_ls) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) out_ls[3 * i + a] = f.sig[a];
   }
   if (out_rot) reinterpret_cast<float4*>(out_rot)[i] = make_float4(f.qn[0], f.qn[1], f.qn[2], f.qn[3]);
-}
-
-// d(v / |v|) adjoint: dv = (dn - n (n . dn)) / |v|
-__device__ __forceinline__ void norm_adj(const float* n, float len, const float* dn, float* dv) {
-  const float p = n[0] * dn[0] + n[1] * dn[1] + n[2] * dn[2] + n[3] * dn[3];
-#pragma unroll
-  for (int a = 0; a < 4; ++a) dv[a] = (dn[a] - n[a] * p) / len;
 }
 
 constexpr int kRegThreads = 256;
@@ -178,34 +146,13 @@ __global__ void __launch_bounds__(kRegThreads) k_regist_bwd(int K, const float* 
       dd[a] = P.R[a] * dp[0] + P.R[3 + a] * dp[1] + P.R[6 + a] * dp[2];
     }
     float ds = dd[0] * f.u[0] + dd[1] * f.u[1] + dd[2] * f.u[2];
-    // cov6 = strip(L L^T): dL = (G + G^T) L with G holding the six upstream values in the upper triangle
+    // cov6 = strip(L L^T)
     const float g6[6] = {gc[6 * i], gc[6 * i + 1], gc[6 * i + 2], gc[6 * i + 3], gc[6 * i + 4], gc[6 * i + 5]};
-    const float S[9] = {2.f * g6[0], g6[1], g6[2], g6[1], 2.f * g6[3], g6[4], g6[2], g6[4], 2.f * g6[5]};
-    float Lm[9];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int b = 0; b < 3; ++b) Lm[3 * a + b] = f.M[3 * a + b] * f.e[b];
     float dM[9];
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      float de = 0.f;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const float dLab = S[3 * a] * Lm[b] + S[3 * a + 1] * Lm[3 + b] + S[3 * a + 2] * Lm[6 + b];
-        dM[3 * a + b] = dLab * f.e[b];
-        de += dLab * f.M[3 * a + b];
-      }
-      ds += de * f.e[b] / P.s;          // e = mod exp(ls + log s): de/ds = e / s
-    }
+    cov6_adj(g6, f.M, f.e, dM, [&](int b, float de) { ds += de * f.e[b] / P.s; });      // e = mod exp(ls + log s): de/ds = e / s
     acc[13] += (double)ds;
-    // build_rotation adjoint w.r.t. qb = (r, x, y, z)
-    const float r = f.qb[0], x = f.qb[1], y = f.qb[2], z = f.qb[3];
     float dqb[4];
-    dqb[0] = 2.f * (-z * dM[1] + y * dM[2] + z * dM[3] - x * dM[5] - y * dM[6] + x * dM[7]);
-    dqb[1] = 2.f * (y * dM[1] + z * dM[2] + y * dM[3] - 2.f * x * dM[4] - r * dM[5] + z * dM[6] + r * dM[7] - 2.f * x * dM[8]);
-    dqb[2] = 2.f * (-2.f * y * dM[0] + x * dM[1] + r * dM[2] + x * dM[3] + z * dM[5] - r * dM[6] + z * dM[7] - 2.f * y * dM[8]);
-    dqb[3] = 2.f * (-2.f * z * dM[0] - r * dM[1] + x * dM[2] + r * dM[3] - 2.f * z * dM[4] + y * dM[5] + x * dM[6] + y * dM[7]);
+    quat_rot_adj(f.qb, dM, dqb);
     float dqn[4], dqm[4];
     norm_adj(f.qb, f.ln, dqb, dqn);      // build_rotation's own normalisation
     norm_adj(f.qn, f.lm, dqn, dqm);      // F.normalize of the product

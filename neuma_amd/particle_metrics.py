@@ -1,7 +1,7 @@
 """Particle-accuracy metrics of modules/tune/metrics.py on the GPU, name for name: `chamfer_distance`,
 `chamfer_distance_kdtree`, `chamfer_distance_naive` and `get_nearest_neighbors_indices_batch`.  The reference builds one scipy
 cKDTree per batch item on the host; here every nearest-neighbour search is the exact grid search of one HIP entry point,
-`nm_chamfer` / `nm_nearest_neighbors` (csrc/nm_nn.hip).
+`nm_chamfer` / `nm_nearest_neighbors` (csrc/nm_nn.hip); `k_nearest_neighbors` is the same search for 1 <= k <= 16 (`nm_knn`).
 
 GPU tensors only: a CPU tensor raises NeumaHipError (there is no CPU path).  Coordinates are searched on fp32 copies, so fp64
 inputs are rounded to fp32 first; the squared distances are computed in fp64 from those fp32 values, and the winner is the
@@ -62,6 +62,23 @@ def nearest_neighbors(query, target):
     ws = torch.empty(max(int(lib.nm_nn_workspace(b, n, m)), 1), dtype=torch.uint8, device=q.device)
     L.check(lib.nm_nearest_neighbors(b, n, m, L.ptr(q), L.ptr(t), idx.data_ptr(), d2.data_ptr(), L.ptr(ws), ws.numel(),
                                      L.stream_ptr(q.device)), "nm_nearest_neighbors")
+    return idx, d2
+
+
+def k_nearest_neighbors(query, target, k, exclude_same_index=False):
+    """One nm_knn call: (idx[B, N, k] int64, d2[B, N, k] fp64), every query point's k nearest target points in ascending
+    (distance^2, index) order, 1 <= k <= 16.  exclude_same_index (query and target are the same cloud): target i is no
+    neighbour of query i, whatever its distance."""
+    _check_clouds(query, target)
+    lib = L.lib()
+    q = query.detach().float().contiguous()
+    t = target.detach().float().contiguous()
+    b, n, m, k = int(q.shape[0]), int(q.shape[1]), int(t.shape[1]), int(k)
+    idx = torch.empty(b, n, max(k, 0), dtype=torch.int64, device=q.device)
+    d2 = torch.empty(b, n, max(k, 0), dtype=torch.float64, device=q.device)
+    ws = torch.empty(max(int(lib.nm_knn_workspace(b, n, m, k)), 1), dtype=torch.uint8, device=q.device)
+    L.check(lib.nm_knn(b, n, m, k, 1 if exclude_same_index else 0, L.ptr(q), L.ptr(t), idx.data_ptr(), d2.data_ptr(), L.ptr(ws),
+                       ws.numel(), L.stream_ptr(q.device)), "nm_knn")
     return idx, d2
 
 

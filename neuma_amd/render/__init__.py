@@ -85,6 +85,34 @@ def build_cov3D(scales: Tensor, rotations: Tensor, scale_modifier: float = 1.0) 
     return torch.stack([S[:, 0, 0], S[:, 0, 1], S[:, 0, 2], S[:, 1, 1], S[:, 1, 2], S[:, 2, 2]], -1)
 
 
+def gaussian_activate(log_scales: Tensor, rot: Tensor, opacity_logit: Optional[Tensor], scale_modifier: float = 1.0,
+                      want_cov: bool = True, want_opacity: bool = True):
+    """nm_gaussian_activate: (cov6 (K,6) = build_cov3D(exp(log_scales), rot, scale_modifier), opacity (K,1) = sigmoid(logit)) of
+    contiguous fp32 GPU tensors, outside autograd; an output that is not wanted is None."""
+    K = log_scales.shape[0]
+    dev = log_scales.device
+    cov6 = torch.empty(K, 6, dtype=torch.float32, device=dev) if want_cov else None
+    op = torch.empty(K, 1, dtype=torch.float32, device=dev) if want_opacity else None
+    L.check(L.lib().nm_gaussian_activate(K, L.ptr(log_scales), L.ptr(rot), L.ptr(opacity_logit), float(scale_modifier), L.ptr(cov6),
+                                         L.ptr(op), L.stream_ptr(dev)), "nm_gaussian_activate")
+    return cov6, op
+
+
+def gaussian_activate_backward(log_scales: Tensor, rot: Tensor, opacity_logit: Optional[Tensor], scale_modifier: float,
+                               dcov6: Optional[Tensor], dopacity: Optional[Tensor]):
+    """nm_gaussian_activate_backward: (dlog_scales (K,3), drot (K,4), dopacity_logit (K,1)); the first two are None without
+    dcov6, the last without dopacity."""
+    K = log_scales.shape[0]
+    dev = log_scales.device
+    dls = torch.empty(K, 3, dtype=torch.float32, device=dev) if dcov6 is not None else None
+    drot = torch.empty(K, 4, dtype=torch.float32, device=dev) if dcov6 is not None else None
+    dlogit = torch.empty(K, 1, dtype=torch.float32, device=dev) if dopacity is not None else None
+    L.check(L.lib().nm_gaussian_activate_backward(K, L.ptr(log_scales), L.ptr(rot), L.ptr(opacity_logit), float(scale_modifier),
+                                                  L.ptr(dcov6), L.ptr(dopacity), L.ptr(dls), L.ptr(drot), L.ptr(dlogit),
+                                                  L.stream_ptr(dev)), "nm_gaussian_activate_backward")
+    return dls, drot, dlogit
+
+
 def _raster_inputs(means3D, shs, colors_precomp, opacities, cov3D):
     m3 = means3D.detach().float().contiguous()
     op = opacities.detach().float().contiguous()
