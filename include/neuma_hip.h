@@ -643,6 +643,48 @@ size_t nm_mesh_inside_workspace(int32_t n_tris, int32_t n_points);
 int nm_points_in_mesh(int32_t n_verts, int32_t n_tris, int32_t n_points, const double* verts, const int32_t* tris,
                       const double* points, uint8_t* inside_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ Gaussian fill (particles out of the density field) */
+
+/* Particles from the opacity density of the Gaussians themselves (neuma_amd/gaussian_fill.py; extras/gaussian_fill.py states
+ * the algorithm in numpy fp64 and computes the lattice for both).  Lattice: `origin` (3 HOST doubles, low corner of cell
+ * (0,0,0)), cell edge h, `dims` (3 HOST ints, at most 2^27 cells); linear cell index (ix ny + iy) nz + iz.  The lattice is
+ * cut into blocks of 4 x 4 x 4 cells, n_blocks = prod(ceil(dims / 4)).
+ *   nm_fill_gaussians  per Gaussian, in fp64: inv(cov) by cofactors and the blocks under the box of its ellipsoid
+ *                      m <= cutoff (half extent sqrt(cutoff cov_ii), clamped to the lattice).  g10 (K, 10) = mean, the six
+ *                      unique entries of inv(cov) (xx xy xz yy yz zz), opacity; boxes (K, 6) int32 = low and high block per
+ *                      axis; counts (K) int32 = blocks under the box.  A Gaussian whose determinant is not a positive
+ *                      finite number (or whose inverse does not fit fp32) gets count 0 and opacity 0: it contributes
+ *                      nothing.  totals (2 DEVICE int64) = {sum of counts, Gaussians skipped}: the caller reads them back.
+ *   nm_fill_density    field (ncells, fp32): d(c) = sum over k with m_k <= cutoff of o_k exp(-m_k / 2) at every cell centre
+ *                      c = origin + (i + 1/2) h (fp64, rounded to fp32 once), m_k = (c - mu_k)^T inv(cov_k) (c - mu_k) in
+ *                      fp32.  The (block, Gaussian) pairs are sorted (rocPRIM) and one wave per block sums its list in
+ *                      ascending Gaussian index: no float atomics, two calls give identical bytes; every cell is written.
+ *                      n_pairs = totals[0], below 2^31.  workspace: nm_fill_density_workspace(K, n_pairs, n_blocks) bytes
+ *                      (0 = invalid sizes).
+ *   nm_fill_classify   on ANY field: kind_cell (ncells, uint8) = 1 where field > density_thres (shell), 2 where not, and on
+ *                      each of the three axis lines through the cell there is a shell cell at a strictly lower and one at
+ *                      a strictly higher index (enclosed), else 0.  Kept = enclosed, plus shell when include_shell.
+ *                      offsets (ncells, int32) = number of kept cells before each cell; counts (3 DEVICE int32) = {kept,
+ *                      shell, enclosed}: the caller reads them back to size the output.  workspace:
+ *                      nm_fill_classify_workspace(dims) bytes.
+ *   nm_fill_emit       per kept cell, in ascending linear index, per_cell^3 points origin_a + (i_a + (s_a + 1/2) / per_cell) h,
+ *                      s nested x, y, z, each evaluated in fp64 by that expression and rounded to fp32 once:
+ *                      points (n_kept per_cell^3, 3) fp32, kind_out (n_kept per_cell^3) uint8 (1 shell, 2 enclosed).
+ * Invalid sizes or a too small workspace fail before any device work; no entry synchronises with the host. */
+int nm_fill_gaussians(int32_t K, const float* means, const float* cov6, const float* opacity, const double* origin, double h,
+                      const int32_t* dims, float cutoff, float* g10, int32_t* boxes, int32_t* counts, int64_t* totals,
+                      void* stream);
+size_t nm_fill_density_workspace(int32_t K, int64_t n_pairs, int32_t n_blocks);
+int nm_fill_density(int32_t K, int64_t n_pairs, const float* g10, const int32_t* boxes, const int32_t* counts,
+                    const double* origin, double h, const int32_t* dims, float cutoff, float* field, void* workspace,
+                    size_t workspace_bytes, void* stream);
+size_t nm_fill_classify_workspace(const int32_t* dims);
+int nm_fill_classify(const int32_t* dims, const float* field, float density_thres, int32_t include_shell, uint8_t* kind_cell,
+                     int32_t* offsets, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int nm_fill_emit(const int32_t* dims, const double* origin, double h, int32_t per_cell, int32_t include_shell,
+                 const uint8_t* kind_cell, const int32_t* offsets, int64_t n_kept, float* points, uint8_t* kind_out,
+                 void* stream);
+
 /* ------------------------------------------------------------------ classical constitutive laws (material/classical.py) */
 
 /* The closed-form laws of the reference's nclaw/material/preset.py:30-282, one thread per particle.  `law`: */

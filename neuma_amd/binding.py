@@ -41,9 +41,18 @@ def _grid_for(particles: Tensor, max_cells: int = 1 << 21) -> Tuple[np.ndarray, 
 
 def build_bindings(means: Tensor, cov6: Tensor, particles: Tensor, confidence: float = 0.95, max_particles: int = 10,
                    return_distances: bool = False):
-    """-> (counts (K,) int32, n_inside (K,) int32, cols (K, max_particles) int32 [-1 padded], [pvals])."""
-    lib = L.lib()
+    """-> (counts (K,) int32, n_inside (K,) int32, cols (K, max_particles) int32 [-1 padded], [pvals]).  Tensors that do not
+    live on a GPU take the numpy path of extras/binding_cpu.py (asset preparation with device="cpu")."""
     dev = means.device
+    if dev.type != "cuda":
+        from .extras import binding_cpu
+        if not 1 <= int(max_particles) <= 16:
+            raise L.NeumaHipError("max_particles must be in [1,16]")
+        out = binding_cpu.build_bindings(means.detach().numpy(), cov6.detach().numpy(), particles.detach().cpu().numpy(),
+                                         chi2_threshold(confidence), int(max_particles))
+        out = tuple(torch.from_numpy(a) for a in out)
+        return out if return_distances else out[:3]
+    lib = L.lib()
     m = means.detach().float().contiguous()
     c = cov6.detach().float().reshape(-1, 6).contiguous()
     x = particles.detach().float().contiguous()

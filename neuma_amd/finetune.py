@@ -38,12 +38,9 @@ def parse_args(argv=None):
     return p.parse_args(argv)
 
 
-def setup(cfg: Cfg, device, for_eval: bool = False):
-    """Everything both drivers build before their loops: asset preparation, dataset, bindings, Gaussians, the nets with
-    the base checkpoint, the particle set.  Returns a dict."""
-    assets = Path(cfg.get("assets_root", "experiments/assets"))
-    data_root = assets / cfg.sim_data_name
-    data_root.mkdir(parents=True, exist_ok=True)
+def _prepare(cfg: Cfg, data_root: Path, device, for_eval: bool = False) -> None:
+    """The assets of cfg.sim_data_name from what cfg.particle_data names, in this order: particles_path, mesh_path, fill (the
+    keywords of gaussian_fill.fill_from_gaussians).  With none of them an evaluation run uses the assets already there."""
     pd = cfg.particle_data
     common = dict(save_dir=data_root, kernels_path=Path(cfg.gaussian.kernels_path), sh_degree=cfg.gaussian.sh_degree,
                   opacity_thres=cfg.gaussian.opacity_thres, confidence=cfg.gaussian.confidence, max_particles=cfg.gaussian.max_particles,
@@ -53,8 +50,19 @@ def setup(cfg: Cfg, device, for_eval: bool = False):
     elif pd.get("mesh_path") is not None:
         prepare_simulation_data(mesh_path=Path(pd.mesh_path), mesh_sample_mode=pd.get("mesh_sample_mode", "volumetric"),
                                 mesh_sample_resolution=pd.get("mesh_sample_resolution", 30), particles_downsample_factor=1, **common)
+    elif pd.get("fill") is not None:
+        prepare_simulation_data(fill=dict(pd.fill), particles_downsample_factor=1, **common)
     elif not for_eval:
         raise ValueError("Either 'particles_path' or 'mesh_path' must be provided in configuration.")
+
+
+def setup(cfg: Cfg, device, for_eval: bool = False):
+    """Everything both drivers build before their loops: asset preparation, dataset, bindings, Gaussians, the nets with
+    the base checkpoint, the particle set.  Returns a dict."""
+    assets = Path(cfg.get("assets_root", "experiments/assets"))
+    data_root = assets / cfg.sim_data_name
+    data_root.mkdir(parents=True, exist_ok=True)
+    _prepare(cfg, data_root, device, for_eval)
     cfg.video_data.device = str(device)                                      # finetune.py:582
     dataset = VideoDataset(cfg.video_data)
     bindings, n_particles = nio.load_bindings(data_root / "bindings.pt", device=device)

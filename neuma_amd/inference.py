@@ -68,20 +68,30 @@ def sample_vel(cfg, seed=None):
     return lin_vel, ang_vel
 
 
+def _prepare(obj_cfg: Cfg, data_root: Path, device) -> None:
+    """The object's assets from what its particle_data names (particles_path, then mesh_path, then fill: the keywords of
+    gaussian_fill.fill_from_gaussians); with none of them the assets already in data_root are used."""
+    pd, gc = obj_cfg.particle_data, obj_cfg.gaussian
+    if pd.get("particles_path") is None and pd.get("mesh_path") is None and pd.get("fill") is None:
+        return
+    data_root.mkdir(parents=True, exist_ok=True)
+    common = dict(save_dir=data_root, kernels_path=Path(gc.kernels_path), sh_degree=gc.sh_degree, opacity_thres=gc.opacity_thres,
+                  confidence=gc.confidence, max_particles=gc.max_particles, device=device)
+    if pd.get("particles_path") is not None:
+        prepare_simulation_data(particles_path=Path(pd.particles_path), particles_downsample_factor=pd.downsample_factor, **common)
+    elif pd.get("mesh_path") is not None:
+        prepare_simulation_data(mesh_path=Path(pd.mesh_path), mesh_sample_mode=pd.mesh_sample_mode,
+                                mesh_sample_resolution=pd.mesh_sample_resolution, particles_downsample_factor=1, **common)
+    else:
+        prepare_simulation_data(fill=dict(pd.fill), particles_downsample_factor=1, **common)
+
+
 def load_object(obj_cfg: Cfg, assets: Path, eval_steps: int, device) -> SceneObject:
     """One entry of cfg.objects -> SceneObject (inference.py:159-254)."""
     data_root = assets / obj_cfg.sim_data_name
     print(f"\nLoad data for {obj_cfg.sim_data_name} ...")
     pd, gc = obj_cfg.particle_data, obj_cfg.gaussian
-    if pd.get("particles_path") is not None or pd.get("mesh_path") is not None:
-        data_root.mkdir(parents=True, exist_ok=True)
-        common = dict(save_dir=data_root, kernels_path=Path(gc.kernels_path), sh_degree=gc.sh_degree, opacity_thres=gc.opacity_thres,
-                      confidence=gc.confidence, max_particles=gc.max_particles, device=device)
-        if pd.get("particles_path") is not None:
-            prepare_simulation_data(particles_path=Path(pd.particles_path), particles_downsample_factor=pd.downsample_factor, **common)
-        else:
-            prepare_simulation_data(mesh_path=Path(pd.mesh_path), mesh_sample_mode=pd.mesh_sample_mode,
-                                    mesh_sample_resolution=pd.mesh_sample_resolution, particles_downsample_factor=1, **common)
+    _prepare(obj_cfg, data_root, device)
     bindings, n_particles = nio.load_bindings(data_root / "bindings.pt", device=device)
     print(f"#Gaussians with particle bindings: {int((n_particles > 0).sum())}")
     print(f"#Avg particles: {float(n_particles.mean())}")

@@ -9,12 +9,15 @@ The O(K N) Mahalanobis loop of binding_utils.py runs as the grid-hashed HIP sear
 Particles out of a mesh (particle_data.mesh_path, tune/utils.py:49-200): 'volumetric' / 'uniform' are sampled here with a
 ray-parity inside test (mesh_inside.sample_mesh_points on a GPU device, extras.mesh_sampling's on the CPU - the same
 particles; the reference calls trimesh and a prebuilt `VolumeSampling` ELF); a particles.ply already lying in the asset folder
-is used as it is."""
+is used as it is.  With neither a particle cloud nor a mesh, `fill` (particle_data.fill: a mapping with the keywords of
+gaussian_fill.fill_from_gaussians - resolution, density_thres, cutoff, per_cell, include_shell) fills the volume the
+opacity-pruned Gaussians themselves describe (gaussian_fill.py; not in the reference)."""
 from pathlib import Path
 from typing import Optional
 
 import torch
 
+from . import gaussian_fill
 from . import io as nio
 from . import mesh_inside
 from .extras import mesh_sampling as mesh      # (outside the section-8 scope: see its header)
@@ -25,7 +28,7 @@ from .binding import prepare_bindings
 def prepare_simulation_data(save_dir: Path, kernels_path: Path, particles_path: Optional[Path] = None, mesh_path: Optional[Path] = None,
                             mesh_sample_mode: str = "volumetric", mesh_sample_resolution: int = 30, sh_degree: int = 3,
                             opacity_thres: float = 0.02, particles_downsample_factor: int = 3, confidence: float = 0.95,
-                            max_particles: int = 10, device="cuda") -> None:
+                            max_particles: int = 10, device="cuda", fill: Optional[dict] = None) -> None:
     save_dir = Path(save_dir)
     done = all((save_dir / n).is_file() for n in ("kernels.ply", "particles.ply", "bindings.pt"))
     print("===================================")
@@ -43,7 +46,7 @@ def prepare_simulation_data(save_dir: Path, kernels_path: Path, particles_path: 
     if particles_path is not None:
         print(f"Extracting particles from pcd file [{particles_path}] ...")
         particles = nio.load_particles_ply(particles_path)
-    elif mesh_path is not None and (save_dir / "particles.ply").is_file():
+    elif (mesh_path is not None or fill is not None) and (save_dir / "particles.ply").is_file():
         # particles sampled elsewhere (e.g. with the reference's tools) and placed in the asset folder: used as they are
         print(f"Using the particles found in [{save_dir / 'particles.ply'}] ...")
         particles = nio.load_particles_ply(save_dir / "particles.ply")
@@ -57,6 +60,12 @@ def prepare_simulation_data(save_dir: Path, kernels_path: Path, particles_path: 
                                                        device=device)
         else:
             particles = mesh.sample_mesh_points(verts, tris, mode=mesh_sample_mode, resolution=int(mesh_sample_resolution))
+        particles_downsample_factor = 1
+    elif fill is not None:
+        print(f"Filling the Gaussians' density field with particles ({dict(fill)}) ...")
+        particles, _, info = gaussian_fill.fill_from_gaussians(gaussians.get_xyz, gaussians.get_covariance(),
+                                                               gaussians.get_opacity.squeeze(-1), device=device, **dict(fill))
+        print(f"lattice {info['dims']}: {info['n_shell']} shell and {info['n_enclosed']} enclosed cells, {len(particles)} particles")
         particles_downsample_factor = 1
     else:
         raise ValueError("Either 'particles_path' or 'mesh_path' must be provided.")
