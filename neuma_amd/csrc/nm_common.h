@@ -165,8 +165,12 @@ NM_HD M3 m3_cofactor(const M3& A) {
 // ---------------------------------------------------------------- 3x3 SVD (one-sided Jacobi)
 // A = U diag(s) V^T with U, V in SO(3), s0 >= s1 >= |s2|, sign(s2) = sign(det A): the convention
 // modules/nclaw/warp/svd.py:61-96 produces from wp.svd3 + its det fix-up.
-// Hestenes rotations act on the columns of B = A V directly (no A^T A squaring), so small singular
-// values keep full relative accuracy.
+// Hestenes rotations act on the columns of B = A V directly (no A^T A squaring).
+// Accuracy the tests hold it to (tests/svd_cases.py, on the host and on the device, condition numbers up to 1e6, exact and
+// near ties, rank loss, permutations, reflections, any scale from 2^-100 to 2^60): reconstruction, orthogonality of U and
+// V, and sigma against fp64 all ABSOLUTE, about 1e-6 sigma_max.  A small singular value of a dense matrix is therefore
+// only known to about eps * cond relative to itself.  The input is normalised by an exact power of two first, so the
+// factors are bitwise independent of the scale of A and sigma scales with it exactly.
 // fast 1-ulp device transcendentals (v_rcp_f32 / v_rsq_f32 / v_sqrt_f32): the IEEE-rounded forms expand to 10-15 VALU
 // instructions each and the Jacobi iteration is self-correcting
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -213,12 +217,26 @@ NM_HD void nm_swap_cols(float* __restrict__ B, float* __restrict__ V, int p, int
     V[3 * r + q] = doit ? -vp : vq;
   }
 }
+NM_HD float nm_bits_to_float(uint32_t u) { return __builtin_bit_cast(float, u); }
+NM_HD uint32_t nm_float_to_bits(float f) { return __builtin_bit_cast(uint32_t, f); }
 NM_HD void nm_svd3(const M3& A, M3& U, float s[3], M3& Vm) {
   float B[9], V[9];
+  // normalise by an exact power of two taken from the exponent field of max|a_ij| (integer compare: the bit patterns of
+  // non-negative floats order as the values do), so that the largest entry lands in [1, 2) ([2^-23, 1) for a subnormal one,
+  // [2, 4) for the top binade: both factors must be normal numbers).  Every product below then stays far from overflow
+  // and underflow, nothing rounds differently, and U, V do not depend on the scale of A at all.  A zero matrix keeps
+  // factor 1; Inf / NaN entries stay what they are.
+  uint32_t mx = 0u;
 #pragma unroll
-  for (int i = 0; i < 9; ++i) { B[i] = A.m[i]; V[i] = (i % 4 == 0) ? 1.f : 0.f; }
-  // at most 5 sweeps (enough for fp32 on any input); a particle stops as soon as a whole sweep found all three pairs
-  // orthogonal to rounding, so the result of a particle never depends on its wave-mates
+  for (int i = 0; i < 9; ++i) { uint32_t u = nm_float_to_bits(A.m[i]) & 0x7fffffffu; mx = u > mx ? u : mx; }
+  int ef = 254 - (int)(mx >> 23);
+  ef = ef < 1 ? 1 : (ef > 253 ? 253 : ef);
+  ef = mx == 0u ? 127 : ef;
+  const float down = nm_bits_to_float((uint32_t)ef << 23), up = nm_bits_to_float((uint32_t)(254 - ef) << 23);
+#pragma unroll
+  for (int i = 0; i < 9; ++i) { B[i] = A.m[i] * down; V[i] = (i % 4 == 0) ? 1.f : 0.f; }
+  // at most 5 sweeps; a particle stops as soon as a whole sweep found all three pairs orthogonal to rounding, and no lane
+  // reads another lane's data, so the result of a particle never depends on its wave-mates
 #pragma unroll 1
   for (int sweep = 0; sweep < 5; ++sweep) {
     bool c01 = nm_jacobi_pair(B, V, 0, 1);
@@ -256,13 +274,13 @@ NM_HD void nm_svd3(const M3& A, M3& U, float s[3], M3& Vm) {
   U.m[0] = u00; U.m[1] = u01; U.m[2] = u02;
   U.m[3] = u10; U.m[4] = u11; U.m[5] = u12;
   U.m[6] = u20; U.m[7] = u21; U.m[8] = u22;
-  s[0] = s0; s[1] = s1; s[2] = s2;
+  s[0] = s0 * up; s[1] = s1 * up; s[2] = s2 * up;   // exact (a power of two) unless the true sigma leaves the fp32 range
 #pragma unroll
   for (int i = 0; i < 9; ++i) Vm.m[i] = V[i];
 }
 
 // adjoint of nm_svd3 with the clamped denominators of warp's adj_svd3: gF from (gU, gs, gVh).
-// E_ab = 1 / min(s_b^2 - s_a^2, -1e-6) for a < b.
+// E_ab = 1 / min(s_b^2 - s_a^2, -1e-6) for a < b, with s_b^2 - s_a^2 evaluated as (s_b - s_a) (s_b + s_a).
 NM_HD M3 nm_svd3_adj(const M3& Um, const float s[3], const M3& Vhm, const M3& gUm, const float g[3], const M3& gVhm) {
   M3 UtgU = m3_mul_tn(Um, gUm);
   M3 VtgV = m3_mul_nt(Vhm, gVhm);  // V^T gV = Vh (gVh)^T
@@ -273,7 +291,9 @@ NM_HD M3 nm_svd3_adj(const M3& Um, const float s[3], const M3& Vhm, const M3& gU
     for (int j = 0; j < 3; ++j) {
       if (i == j) { inner.m[4 * i] = g[i]; continue; }
       int a = i < j ? i : j, b = i < j ? j : i;
-      float e = 1.f / fminf(s[b] * s[b] - s[a] * s[a], -1e-6f);
+      // the difference of squares in factored form: s_b - s_a is exact for close values, so the denominator keeps full
+      // relative accuracy next to the clamp (the rounded squares of two values a few ulps apart differ by 100 % noise)
+      float e = 1.f / fminf((s[b] - s[a]) * (s[b] + s[a]), -1e-6f);
       if (i > j) e = -e;
       float su = e * (UtgU.m[3 * i + j] - UtgU.m[3 * j + i]);
       float sv = e * (VtgV.m[3 * i + j] - VtgV.m[3 * j + i]);

@@ -120,6 +120,28 @@ def build_statics(model, vol, rho, clip, en, device):
     return st
 
 
+def material_nets(name, golden_dir, lora=True):
+    """(golden arrays, elasticity net, plasticity net) of one shipped checkpoint on the GPU, optionally with the golden's LoRA factors"""
+    from neuma_amd.material import InvariantFullMetaElasticity, InvariantFullMetaPlasticity
+    g = np.load(golden_dir / f"material_{name}.npz")
+    b = np.load(golden_dir / "base_models.npz")
+    cfg = dict(layer_widths=[64, 64], norm=None, nonlinearity="gelu", no_bias=True, normalize_input=True, alpha=1e-3)
+    E = InvariantFullMetaElasticity(cfg)
+    P = InvariantFullMetaPlasticity(cfg)
+    for net, t in ((E, "e"), (P, "p")):
+        sd = {"layers.0.fc.weight": torch.tensor(b[f"{name}_{t}_w0"]), "layers.1.fc.weight": torch.tensor(b[f"{name}_{t}_w1"]),
+              "final_layer.fc.weight": torch.tensor(b[f"{name}_{t}_w2"])}
+        print(net.load_state_dict(sd))          # reference checkpoint keys load unchanged
+        if lora:
+            net.init_lora_layers(r=16, lora_alpha=16)
+            net.freeze_all_except_lora()
+            for i, lin in enumerate((net.layers[0].fc, net.layers[1].fc, net.final_layer.fc)):
+                lin.lora_A.data = torch.tensor(g[f"{t}_A{i}"]).float()
+                lin.lora_B.data = torch.tensor(g[f"{t}_B{i}"]).float()
+        net.to(dev())
+    return g, E, P
+
+
 def parity(case: str, name: str, measured: float, bound: float, noise=None) -> None:
     """Record one measured parity error next to the bound it is held to (and, where a fixture carries the reference's own fp32
     run, the distance of that run from its fp64 run): printed (`pytest -s`, or the captured log) and appended to

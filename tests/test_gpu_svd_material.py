@@ -5,7 +5,7 @@ import pytest
 import torch
 
 from oracle import material as om
-from gpu_util import dev, rel_max, abs_max, parity
+from gpu_util import dev, rel_max, abs_max, parity, material_nets as _nets
 
 pytestmark = pytest.mark.gpu
 NAMES = ["jelly", "plasticine", "sand"]
@@ -53,27 +53,6 @@ def test_svd_backward_matches_clamped_adjoint():
     _, s2, _ = SVD()(Fg2)
     (gF2,) = torch.autograd.grad((s2 * gs).sum(), Fg2)
     assert abs_max(gF2[gap.to(dev())], gFo[gap]) < 7e-6      # measured 1.8e-06
-
-
-def _nets(name, golden_dir, lora=True):
-    from neuma_amd.material import InvariantFullMetaElasticity, InvariantFullMetaPlasticity
-    g = np.load(golden_dir / f"material_{name}.npz")
-    b = np.load(golden_dir / "base_models.npz")
-    cfg = dict(layer_widths=[64, 64], norm=None, nonlinearity="gelu", no_bias=True, normalize_input=True, alpha=1e-3)
-    E = InvariantFullMetaElasticity(cfg)
-    P = InvariantFullMetaPlasticity(cfg)
-    for net, t in ((E, "e"), (P, "p")):
-        sd = {"layers.0.fc.weight": torch.tensor(b[f"{name}_{t}_w0"]), "layers.1.fc.weight": torch.tensor(b[f"{name}_{t}_w1"]),
-              "final_layer.fc.weight": torch.tensor(b[f"{name}_{t}_w2"])}
-        print(net.load_state_dict(sd))          # reference checkpoint keys load unchanged
-        if lora:
-            net.init_lora_layers(r=16, lora_alpha=16)
-            net.freeze_all_except_lora()
-            for i, lin in enumerate((net.layers[0].fc, net.layers[1].fc, net.final_layer.fc)):
-                lin.lora_A.data = torch.tensor(g[f"{t}_A{i}"]).float()
-                lin.lora_B.data = torch.tensor(g[f"{t}_B{i}"]).float()
-        net.to(dev())
-    return g, E, P
 
 
 @pytest.mark.parametrize("name", NAMES)
