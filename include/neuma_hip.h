@@ -565,6 +565,15 @@ int nm_sh_rotate_backward(int32_t k, int32_t n_coeff, int32_t has_dc, const floa
                           const float* dL_dshs_out, float* dL_dR, float* dL_dshs_in, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* SH colour coefficients rotated with each Gaussian's own deformation: as nm_sh_rotate (same basis, sample directions,
+ * A_l^{-1}, n_coeff / has_dc rule), with one rotation per Gaussian, R_g = U V^T of the project's 3x3 SVD of F_g (nm_svd3_fwd's:
+ * U, V in SO(3), the sign on sigma_2), the rotation part of the polar decomposition and a proper rotation also where
+ * det F < 0.  F (k,3,3) row-major.  R_out: NULL, or (k,3,3), the rotation that was applied.  For a singular or zero F the
+ * polar rotation is not defined: R_out is still what the SVD gives and every output is finite.  shs_out must not be shs_in
+ * (NM_ERR_INVALID).  No reference counterpart: the reference hands the coefficients to the rasterizer unrotated. */
+int nm_sh_rotate_polar(int32_t k, int32_t n_coeff, int32_t has_dc, const float* F, const float* shs_in, float* shs_out,
+                       float* R_out, void* stream);
+
 /* SSIM loss (modules/d3gs/utils/loss_utils.py:26-66, window 11, sigma 1.5, zero padding, size_average) of two (3,H,W) fp32
  * images: *loss_out (device float) += weight * (1 - ssim(img, gt)); dL_dimg (may be NULL) += weight * d(1 - ssim)/dimg.
  * Adds to both, so it composes with nm_pixel_loss called first.  The loss value is deterministic (fixed-order fp64

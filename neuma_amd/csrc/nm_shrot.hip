@@ -10,6 +10,8 @@
 //   nm_sh_rotate_backward  dD = sum_K dL_dout (x) in: every D entry has ONE owning lane per channel that walks the tile in
 //                          LDS with an fp64 accumulator (no cross-lane step is needed), one partial set per workgroup, then
 //                          one workgroup sums them in a fixed order and chains dD -> dR.  No atomics: bitwise reproducible.
+//   nm_sh_rotate_polar     one rotation PER Gaussian, the polar factor of its deformation gradient: nm_svd3 one Gaussian per
+//                          lane, then c'_l = Y_l(R s_k) (A_l^{-1} c_l) per (Gaussian, channel) lane; D_l is never formed.
 #include "nm_common.h"
 
 namespace {
@@ -264,6 +266,72 @@ __global__ void __launch_bounds__(kShThreads) k_sh_rotate_bwd(int K, const float
   if (t < NE) part[(size_t)blockIdx.x * NE + t] = (red[t] + red[NE + t]) + red[2 * NE + t];
 }
 
+// band L of one (Gaussian, channel) rotated in place by the Gaussian's own R (nine floats) without forming D_l:
+//   w = A_l^{-1} c_l,   c'_l,i = sum_k Y_l,i(R s_k) w_k.   Everything between the fp32 load and the fp32 store is fp64.
+template <int L>
+NM_HD void rotate_band_polar(float* __restrict__ c, const float* __restrict__ R) {
+  constexpr int n = band_n(L), r0 = band_row(L), o = band_off(L);
+  double v[n], acc[n];
+#pragma unroll
+  for (int j = 0; j < n; ++j) { v[j] = (double)c[3 * (r0 + j)]; acc[j] = 0.0; }
+#pragma unroll
+  for (int k = 0; k < n; ++k) {
+    double p[3], Y[n], w = 0.0;
+    sh_sample_point(R, k, p);
+    sh_band(L, p, Y);
+#pragma unroll
+    for (int j = 0; j < n; ++j) w += sh_ainv(o + k * n + j) * v[j];
+#pragma unroll
+    for (int i = 0; i < n; ++i) acc[i] += Y[i] * w;
+  }
+#pragma unroll
+  for (int i = 0; i < n; ++i) c[3 * (r0 + i)] = (float)acc[i];
+}
+
+// K different rotations: R_k = U V^T of nm_svd3(F_k), the rotation of the polar decomposition (proper also where det F < 0).
+// Per tile of 64 Gaussians: coefficient rows and F staged through LDS over consecutive floats; the first wave takes one SVD per
+// lane and leaves R where F was (row stride 9: odd, no bank conflict); three waves then own one (Gaussian, channel) each, one
+// channel per wave (rows P, odd, apart).  A Gaussian's result depends on nothing but its own row: not on the tile, not on K.
+template <int NR, int DC>
+__global__ void __launch_bounds__(kShThreads) k_sh_rotate_polar(int K, const float* __restrict__ F, const float* in,
+                                                                float* __restrict__ out, float* __restrict__ R_out /* or NULL */,
+                                                                int vec) {
+  constexpr int S = 3 * (NR + DC), P = S | 1, DEG = deg_of_rows(NR);
+  __shared__ float tile[kShTile * P];
+  __shared__ float rot[kShTile * 9];
+  const int t = threadIdx.x;
+  const int ntiles = (K + kShTile - 1) / kShTile;
+  for (int ti = blockIdx.x; ti < ntiles; ti += gridDim.x) {
+    const int g0 = ti * kShTile, ng = min(kShTile, K - g0);
+    const size_t base = (size_t)g0 * S, fbase = (size_t)g0 * 9;
+    tile_copy<S, P, false>(tile, const_cast<float*>(in) + base, ng * S, vec);
+    for (int e = t; e < ng * 9; e += kShThreads) rot[e] = F[fbase + e];
+    __syncthreads();
+    if (t < ng) {
+      M3 U, V;
+      float s[3];
+      nm_svd3(m3_load(rot + 9 * t), U, s, V);
+      m3_store(rot + 9 * t, m3_mul_nt(U, V));
+    }
+    __syncthreads();
+    if (t < 3 * kShTile) {
+      const int ch = t / kShTile, g = t % kShTile;
+      if (g < ng) {
+        float* c = tile + g * P + 3 * DC + ch;
+        const float* R = rot + 9 * g;
+        rotate_band_polar<1>(c, R);
+        if (DEG >= 2) rotate_band_polar<2>(c, R);
+        if (DEG >= 3) rotate_band_polar<3>(c, R);
+      }
+    }
+    if (R_out)                                              // (uniform: a kernel argument)
+      for (int e = t; e < ng * 9; e += kShThreads) R_out[fbase + e] = rot[e];
+    __syncthreads();
+    tile_copy<S, P, true>(tile, out + base, ng * S, vec);
+    __syncthreads();
+  }
+}
+
 // one workgroup: dD = the partials in a fixed order, then dR[a][b] += sum_{l,k} (dY_l/dp (R s_k) . (dD_l A_l^{-T})[:, k])_a s_k[b]
 __global__ void __launch_bounds__(kShThreads) k_sh_rotate_finish(int deg, int nb, const float* __restrict__ R,
                                                                  const double* __restrict__ part, float* __restrict__ dR) {
@@ -334,6 +402,22 @@ extern "C" int nm_sh_rotate(int32_t k, int32_t n_coeff, int32_t has_dc, const fl
   const int dc = has_dc ? 1 : 0;
   const int vec = (((uintptr_t)shs_in | (uintptr_t)shs_out) % 16 == 0) ? 1 : 0;
   NM_SH_DISPATCH(k_sh_rotate, nr, dc, dim3(sh_blocks(k)), dim3(kShThreads), 0, (hipStream_t)stream, (int)k, R, shs_in, shs_out, vec);
+  NM_LAUNCH_CHECK();
+  return NM_OK;
+}
+
+extern "C" int nm_sh_rotate_polar(int32_t k, int32_t n_coeff, int32_t has_dc, const float* F, const float* shs_in, float* shs_out,
+                                  float* R_out, void* stream) {
+  NM_REQUIRE(k >= 0, "k < 0");
+  const int nr = sh_rest_rows(n_coeff, has_dc);
+  NM_REQUIRE(nr != 0, "n_coeff must be 4, 9, 16 with has_dc = 1 or 3, 8, 15 with has_dc = 0");
+  if (k == 0) return NM_OK;
+  NM_REQUIRE(F && shs_in && shs_out, "null pointer");
+  NM_REQUIRE(shs_out != shs_in, "shs_out must not be shs_in");
+  const int dc = has_dc ? 1 : 0;
+  const int vec = (((uintptr_t)shs_in | (uintptr_t)shs_out) % 16 == 0) ? 1 : 0;
+  NM_SH_DISPATCH(k_sh_rotate_polar, nr, dc, dim3(sh_blocks(k)), dim3(kShThreads), 0, (hipStream_t)stream, (int)k, F, shs_in, shs_out,
+                 R_out, vec);
   NM_LAUNCH_CHECK();
   return NM_OK;
 }

@@ -5,7 +5,10 @@ Per step (render.py:304-332): stress = E(F) -> state.from_torch(stress) -> in-pl
 state.from_torch(F) -> statics_initializer.update(statics, step) -> de-normalise, bind with the PREVIOUS frame's positions,
 render the debug views with the camera of the FIRST step -> <result>/<name>/images_<video_name>/<view>_<frame:03d>.png.
 The YAML's own sim.eps is used here (the reference only overrides it in finetune.py).  Packing the frames into an mp4
-(mediapy) is left to external tools."""
+(mediapy) is left to external tools.
+
+`gaussian.rotate_sh: true` (or --rotate_sh; no reference counterpart): from sh_degree 1 the SH colours turn with each
+Gaussian's deformation - rotate_shs_by_deformation once per frame, before the views; the first frame is untouched."""
 import argparse
 import random
 from pathlib import Path
@@ -17,6 +20,7 @@ from . import io as nio
 from .config import Cfg, load_config
 from .finetune import particle_init_data, setup
 from .sim import MPMForwardSim, MPMModelBuilder, MPMStateInitializer, MPMStaticsInitializer
+from .render.transform_utils import rotate_shs_by_deformation
 from .tune import compute_bindings_F, compute_bindings_xyz, denormalize_points_helper_func, diff_rasterization
 
 RESULT = "experiments/results"
@@ -38,6 +42,7 @@ def parse_args(argv=None):
     p.add_argument("--transform_file", type=str, default=None)
     p.add_argument("--alpha", type=float, default=None)
     p.add_argument("--result_root", type=str, default=RESULT)
+    p.add_argument("--rotate_sh", action="store_true", help="Rotate the SH colours with the deformation (gaussian.rotate_sh).")
     return p.parse_args(argv)
 
 
@@ -107,6 +112,7 @@ def evaluate(cfg: Cfg, on_frame=None):
     state.from_torch(x=x, v=v, C=C, F=F)
     views = [vw for vw in dataset.views if vw in cfg.get("debug_views", [])]
     scal = cfg.gaussian.get("scaling_modifier", 1.0)
+    rotate_sh = bool(cfg.get("rotate_sh", False) or cfg.gaussian.get("rotate_sh", False)) and gaussians.active_sh_degree > 0
     for vw in views:                                                       # first frame: un-deformed kernels (render.py:292-297)
         render = diff_rasterization(gaussians.get_xyz, None, gaussians, dataset.getCameras(vw, first_step), background, scaling_modifier=scal)
         save_image(render, image_root / f"{vw}_{first_step:03d}.png")
@@ -123,13 +129,19 @@ def evaluate(cfg: Cfg, on_frame=None):
         means3D = compute_bindings_xyz(de_x, de_x_prev, g_prev, bindings)
         deform_grad = compute_bindings_F(F, bindings)
         images = {}
+        shs = rotate_shs_by_deformation(gaussians.get_features, deform_grad) if rotate_sh and views else None       # once per frame
         for vw in views:
-            images[vw] = diff_rasterization(means3D, deform_grad, gaussians, dataset.getCameras(vw, first_step), background, scaling_modifier=scal)
+            cam = dataset.getCameras(vw, first_step)
+            if shs is None:
+                images[vw] = diff_rasterization(means3D, deform_grad, gaussians, cam, background, scaling_modifier=scal)
+            else:
+                images[vw] = diff_rasterization(means3D, deform_grad, None, cam, background, gaussians.active_sh_degree,
+                                                gaussians.get_covariance(scaling_modifier=scal), gaussians.get_opacity, shs)
             save_image(images[vw], image_root / f"{vw}_{first_step + step:03d}.png")
         if state_root is not None:
             nio.save_particles_ply(state_root / f"{first_step + step:03d}.ply", x.detach().cpu().numpy())
         if on_frame is not None:
-            on_frame(step, dict(x=x, F=F, means3D=means3D, images=images))
+            on_frame(step, dict(x=x, F=F, means3D=means3D, deform_grad=deform_grad, images=images))
         de_x_prev, g_prev = de_x.clone().detach(), means3D.clone().detach()
     return image_root
 

@@ -94,6 +94,10 @@ def _views(dataset, spec):
 
 
 def finetune(cfg: Cfg, log=print):
+    if bool(cfg.gaussian.get("rotate_sh", False)):
+        raise NotImplementedError("`gaussian.rotate_sh: true` rotates the SH colours with the deformation in the forward renderers only "
+                                  "(python -m neuma_amd.render / neuma_amd.inference): training would need the colours' gradient with "
+                                  "respect to F, which is not propagated.  Remove the key to fine-tune")
     seed = cfg.seed
     random.seed(seed); np.random.seed(seed); torch.manual_seed(seed)
     device = torch.device(f"cuda:{cfg.gpu}")

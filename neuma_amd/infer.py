@@ -35,6 +35,7 @@ class SceneObject:
     gaussians: object            # GaussianModel
     bindings: object             # tune.Bindings or a torch sparse COO tensor (K x N_obj)
     scaling: float = 1.0         # scaling_modifier of the covariances (inference.py obj_scalings)
+    rotate_sh: bool = False      # `gaussian.rotate_sh`: its SH colours turn with its Gaussians' deformation (no reference counterpart)
 
 
 def denormalize_points(points: torch.Tensor, sections: Sequence[int], state_init) -> torch.Tensor:
@@ -49,7 +50,9 @@ def denormalize_points(points: torch.Tensor, sections: Sequence[int], state_init
 def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: int, cameras: Sequence, background: torch.Tensor,
                      denormalize: bool = False, on_frame: Optional[Callable[[int, Dict], None]] = None,
                      render: bool = True) -> Iterator[Dict]:
-    """Generator over frames 0..eval_steps.  Yields {'step', 'x', 'F', 'means3D', 'images': [per camera]}."""
+    """Generator over frames 0..eval_steps.  Yields {'step', 'x', 'F', 'means3D', 'images': [per camera]}, and with `render`
+    'shs', the coefficients the frame was rendered with: those of an object with `rotate_sh` are rotated once per frame, before
+    the views, by the polar rotations of its bound deformation gradients; frame 0 (un-deformed) carries them as loaded."""
     device = model.device
     state_initializer = MPMStateInitializer(model)
     statics_initializer = MPMStaticsInitializer(model)
@@ -77,6 +80,7 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
         shs = torch.cat([g.get_features for g in gs], 0)
         for cam in cameras:
             first["images"].append(diff_rasterization(first["means3D"], None, None, cam, background, sh_deg, cov, opa, shs))
+        first["shs"] = shs
     if on_frame:
         on_frame(0, first)
     yield first
@@ -84,6 +88,7 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
     p_prev = [t.clone().detach() for t in torch.split(de_x, sections, dim=0)]
     k_prev = [g.get_xyz.clone().detach() for g in gs]
     bindings = [o.bindings for o in objects]
+    rotate_sh = [bool(o.rotate_sh) for o in objects] if render and any(o.rotate_sh for o in objects) else None
     for step in range(1, eval_steps + 1):
         stress = elasticity(F)
         state.from_torch(stress=stress)
@@ -95,12 +100,14 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
         p_curr = list(torch.split(de_x, sections, dim=0))
         dgs = list(torch.split(F, sections, dim=0))
         pack = preprocess_for_rasterization(obj_gaussians=gs, obj_deform_grad=dgs, obj_kernels_prev=k_prev, obj_particles_curr=p_curr,
-                                            obj_particles_prev=p_prev, obj_bindings=bindings, obj_scalings=scal)
+                                            obj_particles_prev=p_prev, obj_bindings=bindings, obj_scalings=scal,
+                                            obj_rotate_sh=rotate_sh)
         frame = dict(step=step, x=x.clone(), F=F.clone(), means3D=pack["means3D"], images=[])
         if render:
             for cam in cameras:
                 frame["images"].append(diff_rasterization(pack["means3D"], pack["deform_grad"], None, cam, background,
                                                           pack["active_sh_degree"], pack["cov3D"], pack["opacity"], pack["shs"]))
+            frame["shs"] = pack["shs"]
         if on_frame:
             on_frame(step, frame)
         yield frame

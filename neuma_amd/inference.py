@@ -50,6 +50,7 @@ def parse_args(argv=None):
     p.add_argument("--save_particles", "-sp", type=str, default=None, help="Specify the folder name for saving simulated particles.")
     p.add_argument("--dataset_path", type=str, default=None, help="Rewrite video dataset path.")
     p.add_argument("--result_root", type=str, default=RESULT)
+    p.add_argument("--rotate_sh", action="store_true", help="Rotate every object's SH colours with its deformation (gaussian.rotate_sh).")
     return p.parse_args(argv)
 
 
@@ -86,8 +87,10 @@ def _prepare(obj_cfg: Cfg, data_root: Path, device) -> None:
         prepare_simulation_data(fill=dict(pd.fill), particles_downsample_factor=1, **common)
 
 
-def load_object(obj_cfg: Cfg, assets: Path, eval_steps: int, device) -> SceneObject:
-    """One entry of cfg.objects -> SceneObject (inference.py:159-254)."""
+def load_object(obj_cfg: Cfg, assets: Path, eval_steps: int, device, rotate_sh: bool = False) -> SceneObject:
+    """One entry of cfg.objects -> SceneObject (inference.py:159-254).  `gaussian.rotate_sh: true` in the entry (or `rotate_sh`,
+    the command line's --rotate_sh, for every entry) turns the object's SH colours with its deformation; the reference has no
+    such key."""
     data_root = assets / obj_cfg.sim_data_name
     print(f"\nLoad data for {obj_cfg.sim_data_name} ...")
     pd, gc = obj_cfg.particle_data, obj_cfg.gaussian
@@ -134,7 +137,7 @@ def load_object(obj_cfg: Cfg, assets: Path, eval_steps: int, device) -> SceneObj
     init_data.set_lin_vel(lin_vel)
     init_data.set_ang_vel(ang_vel)
     return SceneObject(init_data=init_data, elasticity=elasticity, plasticity=plasticity, gaussians=gaussians, bindings=bindings,
-                       scaling=float(gc.get("scaling_modifier", 1.0)))
+                       scaling=float(gc.get("scaling_modifier", 1.0)), rotate_sh=bool(rotate_sh or gc.get("rotate_sh", False)))
 
 
 @torch.no_grad()
@@ -165,7 +168,7 @@ def inference(cfg: Cfg, on_frame=None):
     dataset = CameraDataset(cfg.video_data)
     first_step = dataset.steps[0]
     assets = Path(cfg.get("assets_root", "experiments/assets"))
-    objects = [load_object(o, assets, eval_steps, device) for o in cfg.objects]
+    objects = [load_object(o, assets, eval_steps, device, rotate_sh=bool(cfg.get("rotate_sh", False))) for o in cfg.objects]
     views = [vw for vw in dataset.views if vw in debug_views]
     cameras = [dataset.getCameras(vw, first_step) for vw in views]               # the camera of the FIRST step throughout
     for frame in simulate_objects(model, objects, eval_steps, cameras, background, denormalize=bool(cfg.get("denormalize", False))):

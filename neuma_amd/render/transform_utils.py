@@ -97,6 +97,51 @@ def rotate_shs_torch(shs_feat: Tensor, R: Tensor) -> Tensor:
     return torch.cat(parts, 1)
 
 
+def rotate_shs_per_gaussian_torch(shs_rest: Tensor, R: Tensor) -> Tensor:
+    """One rotation per Gaussian through torch ops: shs_rest (K, 3 | 8 | 15, 3), R (K, 3, 3) -> a new tensor, any dtype and
+    device.  The D_l are not formed: with w = A_l^{-1} c_l per channel, c'_l,i = sum_k Y_l,i(R s_k) w_k - the formula of
+    nm_sh_rotate_polar, its CPU path and the tests' yardstick, as `rotate_shs_torch` is for one R."""
+    if shs_rest.shape[1] <= 1:
+        return shs_rest
+    deg = _rest_degree(shs_rest)
+    assert R.shape == (shs_rest.shape[0], 3, 3), f"Rotations must have shape ({shs_rest.shape[0]}, 3, 3), but got {tuple(R.shape)}."
+    R = R.to(shs_rest)
+    dirs, ainv = sh_rotation_tables()
+    parts, lo = [], 0
+    for l in range(1, deg + 1):
+        n = 2 * l + 1
+        s = torch.as_tensor(dirs[:n], dtype=R.dtype, device=R.device)
+        yv = sh_band(l, torch.einsum("gab,kb->gka", R, s))                                # [g][k][i] = Y_i(R_g s_k)
+        w = torch.einsum("kj,gjc->gkc", torch.as_tensor(ainv[l - 1], dtype=R.dtype, device=R.device), shs_rest[:, lo:lo + n])
+        parts.append(torch.einsum("gki,gkc->gic", yv, w))
+        lo += n
+    return torch.cat(parts, 1)
+
+
+def rotate_shs_by_deformation(shs: Tensor, F: Tensor, has_dc: bool = True, return_rotation: bool = False):
+    """nm_sh_rotate_polar: the colours of a roll-out frame turned with each Gaussian's own deformation.  shs (K, n, 3) and the
+    bound deformation gradients F (K, 3, 3), both GPU fp32; R_g = U Vh of the project's SVD of F_g (the rotation of the polar
+    decomposition) and c'_g = diag(1, D_1(R_g), D_2(R_g), D_3(R_g)) c_g.  Returns a NEW tensor, or (it, R (K, 3, 3)) with
+    `return_rotation`; `shs` with one row or fewer is returned as is (R is then None).  Not differentiable: the colour's
+    dependence on F is not propagated, so inputs that require grad are refused while grad mode is on.  The reference has no
+    counterpart (its shs reach the rasterizer unrotated)."""
+    assert shs.dim() == 3 and shs.shape[-1] == 3, f"SH features must be in RGB format (N, SHS_NUM, 3), but got {tuple(shs.shape)}"
+    if torch.is_grad_enabled() and (shs.requires_grad or F.requires_grad):
+        raise RuntimeError("rotate_shs_by_deformation is not differentiable: the colour's dependence on F is not propagated "
+                           "(call it under torch.no_grad() or on detached tensors)")
+    if shs.shape[1] <= 1:
+        return (shs, None) if return_rotation else shs
+    Fc = F.detach().reshape(-1, 3, 3).contiguous()
+    sc = shs.detach().contiguous()
+    assert Fc.shape[0] == sc.shape[0], f"Shape mismatch: shs {sc.shape[0]} F {Fc.shape[0]}"
+    dev = L.same_device(sc, Fc)
+    out = torch.empty_like(sc)
+    R = torch.empty_like(Fc) if return_rotation else None
+    L.check(L.lib().nm_sh_rotate_polar(sc.shape[0], sc.shape[1], int(has_dc), L.ptr(Fc, torch.float32), L.ptr(sc, torch.float32),
+                                       L.ptr(out, torch.float32), L.ptr(R), L.stream_ptr(dev)), "nm_sh_rotate_polar")
+    return (out, R) if return_rotation else out
+
+
 def sh_rotate(shs: Tensor, R9: Tensor, has_dc: bool, out: Optional[Tensor] = None) -> Tensor:
     """nm_sh_rotate: shs (K, n, 3) fp32 on the GPU, R9 nine DEVICE floats (row-major); `out` may be `shs` itself."""
     out = torch.empty_like(shs) if out is None else out

@@ -12,6 +12,7 @@ from torch import Tensor
 
 from . import _lib as L
 from .render import get_rasterizer, deform_cov_by_F
+from .render.transform_utils import rotate_shs_by_deformation
 
 
 class Bindings(object):
@@ -186,8 +187,10 @@ def diff_rasterization(x: Tensor, deform_grad: Optional[Tensor], gaussians, view
                        gaussians_active_sh: Optional[int] = None, guassians_cov: Optional[Tensor] = None,
                        gaussians_opa: Optional[Tensor] = None, gaussians_shs: Optional[Tensor] = None,
                        scaling_modifier: Optional[float] = 1., force_mask_data: Optional[bool] = False,
-                       tile_rows=None) -> Tensor:
-    """tune/utils.py:323-421 (argument names kept, including the reference's `guassians_cov` spelling)."""
+                       tile_rows=None, rotate_sh: bool = False) -> Tensor:
+    """tune/utils.py:323-421 (argument names kept, including the reference's `guassians_cov` spelling).  `rotate_sh` (no
+    reference counterpart, default off): the SH colours turn with each Gaussian's deformation - with `deform_grad` given, a
+    degree above 0 and no `force_mask_data` the rasterizer gets rotate_shs_by_deformation(shs, deform_grad); not differentiable."""
     means3D = x
     if gaussians is not None:
         cov3D_precomp = gaussians.get_covariance(scaling_modifier=scaling_modifier)
@@ -203,6 +206,8 @@ def diff_rasterization(x: Tensor, deform_grad: Optional[Tensor], gaussians, view
         assert cov3D_precomp.shape[0] == tensor_F.shape[0], \
             f"Shape mismatch: cov3D {cov3D_precomp.shape[0]} F {tensor_F.shape[0]}"
         cov3D_deformed = deform_cov_by_F(cov3D_precomp.reshape(-1, 6), tensor_F)
+        if rotate_sh and sh_degree > 0 and not force_mask_data:
+            shs = rotate_shs_by_deformation(shs, tensor_F)
     else:
         cov3D_deformed = cov3D_precomp
     means2D = torch.zeros_like(means3D, requires_grad=True)     # (the reference adds 0 to make it a non-leaf it can retain_grad on)
@@ -219,14 +224,19 @@ def diff_rasterization(x: Tensor, deform_grad: Optional[Tensor], gaussians, view
 
 def preprocess_for_rasterization(obj_gaussians: List, obj_deform_grad: List[Tensor], obj_kernels_prev: List[Tensor],
                                  obj_particles_curr: List[Tensor], obj_particles_prev: List[Tensor],
-                                 obj_bindings: List, obj_scalings: List[float]):
-    """tune/utils.py:475-523 (multi-object concat)."""
+                                 obj_bindings: List, obj_scalings: List[float], obj_rotate_sh: Optional[List[bool]] = None):
+    """tune/utils.py:475-523 (multi-object concat).  `obj_rotate_sh` (no reference counterpart): per object, whether its SH
+    colours turn with its Gaussians' deformation (rotate_shs_by_deformation, before the concatenation)."""
     obj_x = [compute_bindings_xyz(pc, pp, kp, b) for pc, pp, kp, b in
              zip(obj_particles_curr, obj_particles_prev, obj_kernels_prev, obj_bindings)]
     obj_F = [compute_bindings_F(F, b) for F, b in zip(obj_deform_grad, obj_bindings)]
     obj_cov = [g.get_covariance(scaling_modifier=s) for g, s in zip(obj_gaussians, obj_scalings)]
     obj_opa = [g.get_opacity for g in obj_gaussians]
     obj_shs = [g.get_features for g in obj_gaussians]
+    if obj_rotate_sh is not None:
+        assert len(obj_rotate_sh) == len(obj_gaussians), f"obj_rotate_sh: {len(obj_rotate_sh)} flags for {len(obj_gaussians)} objects"
+        obj_shs = [rotate_shs_by_deformation(c, F) if on and g.active_sh_degree > 0 else c
+                   for c, F, on, g in zip(obj_shs, obj_F, obj_rotate_sh, obj_gaussians)]
     return {"means3D": torch.cat(obj_x, 0), "deform_grad": torch.cat(obj_F, 0), "cov3D": torch.cat(obj_cov, 0),
             "opacity": torch.cat(obj_opa, 0), "shs": torch.cat(obj_shs, 0),
             "active_sh_degree": obj_gaussians[0].active_sh_degree}
