@@ -582,6 +582,26 @@ size_t nm_ssim_workspace(int32_t h, int32_t w);
 int nm_ssim_loss(float weight, int32_t h, int32_t w, const float* img, const float* gt, float* loss_out, float* dL_dimg,
                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ particle-state loss (neuma_amd/pretrain.py) */
+
+/* Position + velocity loss of one frame against a recorded trajectory, fused with its gradient.  No reference counterpart
+ * (the reference ships its base models, not their training).  x, v, x_gt, v_gt (n,3) fp32; mask NULL (all rows) or n bytes,
+ * a row is kept where mask != 0; m = kept rows.  kind 0 = l1, 1 = l2:
+ *   term_x = sum over kept rows and 3 components of |x - x_gt| (l1) or (x - x_gt)^2 (l2), divided by 3 m   (F.l1_loss /
+ *   F.mse_loss over the kept rows), term_v likewise;  *loss_out (device float) += weight_x term_x + weight_v term_v;
+ *   terms_out (NULL or 2 device floats) = {term_x, term_v}, unweighted, written;
+ *   dL_dx = weight_x d(term_x)/dx, dL_dv = weight_v d(term_v)/dv: each NULL or (n,3), written (not added), 0 on rows the mask
+ *   drops, and the l1 gradient is 0 where the difference is 0.
+ * m == 0: the loss gains nothing, all gradients are 0.  v_gt == NULL: positions only, weight_v is ignored, v may be NULL and
+ * dL_dv, if given, is written as zeros.  n == 0 is a no-op.  kind outside {0, 1}, a NULL x / x_gt / loss_out / workspace, v_gt
+ * without v, or a workspace smaller than nm_state_loss_workspace(n) (device scratch, 8-byte aligned): NM_ERR_INVALID.
+ * Differences and sums in fp64, per-workgroup partials summed by one workgroup in a fixed order, no float atomics: two calls
+ * give identical bits, and so do 16-byte aligned operands (float4 path) and unaligned ones (scalar path). */
+size_t nm_state_loss_workspace(int32_t n);
+int nm_state_loss(int32_t n, int32_t kind, float weight_x, float weight_v, const float* x, const float* v, const float* x_gt,
+                  const float* v_gt, const uint8_t* mask, float* loss_out, float* terms_out, float* dL_dx, float* dL_dv,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ image-quality metrics (experiments/evaluation.py) */
 
 /* torchmetrics' PeakSignalNoiseRatio and structural_similarity_index_measure (gaussian window 11, sigma 1.5, k1 0.01, k2 0.03,
