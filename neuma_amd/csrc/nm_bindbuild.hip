@@ -13,6 +13,7 @@
 // padded candidate table (K x max_particles, columns ascending) + the number kept per Gaussian, i.e. CSR after one
 // prefix sum - never a dense matrix.
 #include "nm_common.h"
+#include "nm_workspace.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -144,21 +145,20 @@ __global__ void __launch_bounds__(128) k_bind_build(int K, BindGrid g, const flo
   }
 }
 
-static inline size_t bb_al(size_t x) { return (x + 255) & ~(size_t)255; }
 struct BindWs { uint32_t *keys_in, *keys_out, *vals_in, *vals_out; int* cell_start; void* sort_tmp; size_t sort_bytes; size_t total; };
 static BindWs carve_bind_ws(void* base, int N, int ncells) {
-  BindWs w; char* p = (char*)base; size_t o = 0; size_t n = (size_t)(N > 0 ? N : 1);
-  w.keys_in = (uint32_t*)(p + o); o += bb_al(n * 4);
-  w.keys_out = (uint32_t*)(p + o); o += bb_al(n * 4);
-  w.vals_in = (uint32_t*)(p + o); o += bb_al(n * 4);
-  w.vals_out = (uint32_t*)(p + o); o += bb_al(n * 4);
-  w.cell_start = (int*)(p + o); o += bb_al(((size_t)ncells + 2) * 4);
+  BindWs w; NmCarver c(base); size_t n = (size_t)(N > 0 ? N : 1);
+  w.keys_in = c.take<uint32_t>(n);
+  w.keys_out = c.take<uint32_t>(n);
+  w.vals_in = c.take<uint32_t>(n);
+  w.vals_out = c.take<uint32_t>(n);
+  w.cell_start = c.take<int>((size_t)ncells + 2);
   size_t tb = 0;
   rocprim::radix_sort_pairs(nullptr, tb, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0u, 32u,
                             (hipStream_t)0);
   w.sort_bytes = tb;
-  w.sort_tmp = (void*)(p + o); o += bb_al(tb);
-  w.total = o;
+  w.sort_tmp = c.take<char>(tb);
+  w.total = c.total();
   return w;
 }
 

@@ -7,6 +7,7 @@
 // nm_svd3_fwd / nm_svd3_bwd).  Every `where` of the reference is a select of two evaluated values; IEEE division and
 // logf / expf / cbrtf throughout (no fast-math), so a NaN the reference produces is a NaN here.
 #include "nm_common.h"
+#include "nm_reduce.h"
 
 namespace {
 
@@ -342,21 +343,6 @@ __global__ void __launch_bounds__(kClThreads) k_classical_fwd(int n, int mode, c
   m3_store(out + 9 * (size_t)p, cl_forward<LAW>(m3_load(F + 9 * (size_t)p), P, mode));
 }
 
-// block sum of two fp64 accumulators in a fixed order: lanes by xor shuffles, then the four waves left to right
-__device__ __forceinline__ void cl_block_sum2(double acc[2], double* sh) {
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    double v = acc[j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    acc[j] = v;
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sh[2 * wave] = acc[0]; sh[2 * wave + 1] = acc[1]; }
-  __syncthreads();
-  if (threadIdx.x < 2) acc[0] = ((sh[threadIdx.x] + sh[2 + threadIdx.x]) + sh[4 + threadIdx.x]) + sh[6 + threadIdx.x];
-}
-
 template <int LAW>
 __global__ void __launch_bounds__(kClThreads) k_classical_bwd(int n, int mode, const float* __restrict__ sc,
                                                               const float* __restrict__ F, const float* __restrict__ G,
@@ -371,20 +357,15 @@ __global__ void __launch_bounds__(kClThreads) k_classical_bwd(int n, int mode, c
     acc[1] += (double)a1;
   }
   if (LAW == NM_LAW_SIGMA_PLASTIC) return;      // no learnable scalar
-  cl_block_sum2(acc, sh);
-  if (threadIdx.x < 2) part[2 * (size_t)blockIdx.x + threadIdx.x] = acc[0];
+  const auto tot = nm_block_reduce<4, NmSum>(acc, sh);      // nm_reduce.h: the fixed order
+  if (threadIdx.x < 2) part[2 * (size_t)blockIdx.x + threadIdx.x] = tot[threadIdx.x];
 }
 
-// one block: the per-block partials in a fixed order, out[j] = sum
+// one block: the per-block partials, out[j] = sum
 __global__ void __launch_bounds__(kClThreads) k_classical_reduce(int nb, const double* __restrict__ part, float* __restrict__ out) {
   __shared__ double sh[8];
-  double acc[2] = {0.0, 0.0};
-  for (int b = threadIdx.x; b < nb; b += blockDim.x) {
-    acc[0] += part[2 * (size_t)b];
-    acc[1] += part[2 * (size_t)b + 1];
-  }
-  cl_block_sum2(acc, sh);
-  if (threadIdx.x < 2) out[threadIdx.x] = (float)acc[0];
+  const auto tot = nm_block_sum_partials<4, 2>(part, nb, 2, sh);
+  if (threadIdx.x < 2) out[threadIdx.x] = (float)tot[threadIdx.x];
 }
 
 int cl_blocks(int n) {

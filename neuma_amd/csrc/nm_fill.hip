@@ -30,6 +30,7 @@
 // -ffp-contract=off: the fp64 expressions (box, cell centre, emitted coordinate) must round as numpy's do.  The fp32 inner
 // loop of k_fill_density alone opts back into contraction: its result is held to a tolerance, not to bits.
 #include "nm_common.h"
+#include "nm_workspace.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -222,8 +223,6 @@ __global__ void __launch_bounds__(256) k_fill_emit(FillGrid g, int per_cell, int
 
 // ---------------------------------------------------------------- host side
 
-static inline size_t fl_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static int fill_grid(FillGrid* g, const double* origin, double h, const int32_t* dims) {
   NM_REQUIRE(origin && dims, "null lattice");
   NM_REQUIRE(h > 0.0 && h <= 1.7976931348623157e308, "cell edge must be positive and finite");
@@ -257,18 +256,18 @@ extern "C" int nm_fill_gaussians(int32_t K, const float* means, const float* cov
 
 struct FillWs { int* offsets; int* block_start; uint64_t *keys_in, *keys_out; void* tmp; size_t tmp_bytes; size_t total; };
 static FillWs carve_fill_ws(void* base, int K, int64_t n_pairs, int nblocks) {
-  FillWs w; char* p = (char*)base; size_t o = 0;
+  FillWs w; NmCarver c(base);
   const size_t np = (size_t)(n_pairs > 0 ? n_pairs : 1);
-  w.offsets = (int*)(p + o); o += fl_al((size_t)K * 4);
-  w.block_start = (int*)(p + o); o += fl_al(((size_t)nblocks + 2) * 4);
-  w.keys_in = (uint64_t*)(p + o); o += fl_al(np * 8);
-  w.keys_out = (uint64_t*)(p + o); o += fl_al(np * 8);
+  w.offsets = c.take<int>((size_t)K);
+  w.block_start = c.take<int>((size_t)nblocks + 2);
+  w.keys_in = c.take<uint64_t>(np);
+  w.keys_out = c.take<uint64_t>(np);
   size_t sort_b = 0, scan_b = 0;
   rocprim::radix_sort_keys(nullptr, sort_b, (uint64_t*)nullptr, (uint64_t*)nullptr, np, 0u, 64u, (hipStream_t)0);
   rocprim::exclusive_scan(nullptr, scan_b, (int*)nullptr, (int*)nullptr, 0, (size_t)K, rocprim::plus<int>(), (hipStream_t)0);
   w.tmp_bytes = sort_b > scan_b ? sort_b : scan_b;
-  w.tmp = (void*)(p + o); o += fl_al(w.tmp_bytes > 0 ? w.tmp_bytes : 1);
-  w.total = o;
+  w.tmp = c.take<char>(w.tmp_bytes > 0 ? w.tmp_bytes : 1);
+  w.total = c.total();
   return w;
 }
 
@@ -317,19 +316,19 @@ extern "C" int nm_fill_density(int32_t K, int64_t n_pairs, const float* g10, con
 
 struct FillCws { int *first[3], *last[3]; int* keep; void* tmp; size_t tmp_bytes; size_t total; };
 static FillCws carve_fill_cws(void* base, const int32_t* dims) {
-  FillCws w; char* p = (char*)base; size_t o = 0;
+  FillCws w; NmCarver c(base);
   const size_t nc = (size_t)dims[0] * dims[1] * dims[2];
   for (int a = 0; a < 3; ++a) {
     const size_t lines = nc / (size_t)dims[a];
-    w.first[a] = (int*)(p + o); o += fl_al(lines * 4);
-    w.last[a] = (int*)(p + o); o += fl_al(lines * 4);
+    w.first[a] = c.take<int>(lines);
+    w.last[a] = c.take<int>(lines);
   }
-  w.keep = (int*)(p + o); o += fl_al(nc * 4);
+  w.keep = c.take<int>(nc);
   size_t tb = 0;
   rocprim::exclusive_scan(nullptr, tb, (int*)nullptr, (int*)nullptr, 0, nc, rocprim::plus<int>(), (hipStream_t)0);
   w.tmp_bytes = tb;
-  w.tmp = (void*)(p + o); o += fl_al(tb > 0 ? tb : 1);
-  w.total = o;
+  w.tmp = c.take<char>(tb > 0 ? tb : 1);
+  w.total = c.total();
   return w;
 }
 

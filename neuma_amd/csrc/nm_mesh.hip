@@ -19,6 +19,8 @@
 // The formula is evaluated as numpy evaluates it, one rounded operation at a time: no contraction into fma (numpy does not
 // fuse; the Makefile also passes -ffp-contract=off for this file), and fp64 `/` is the correctly rounded division.
 #include "nm_common.h"
+#include "nm_reduce.h"
+#include "nm_workspace.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -54,7 +56,6 @@ struct MiGrid {
 // per-triangle state between the passes (0 = boxed, not yet placed)
 enum : int { kTriDropped = -1, kTriAll = -2, kTriBinned = 1 };
 
-static inline size_t mi_al(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline int mi_cell_budget(int t) { return t <= kTrisPerCell ? 1 : (int)(((int64_t)t + kTrisPerCell - 1) / kTrisPerCell); }
 static inline int mi_prep_blocks(int t) {
   const int g = nm_div_up(t, kMiThreads);
@@ -81,27 +82,27 @@ struct MiWs {
   size_t total;
 };
 
-static MiWs carve(char* base, int t) {
+static MiWs carve(void* base, int t) {
   MiWs w;
   w.gprep = mi_prep_blocks(t); w.cmax = mi_cell_budget(t); w.cap = mi_pair_cap(t);
   const size_t nt = t > 0 ? (size_t)t : 1, nc = (size_t)w.cmax + 1;
-  size_t o = 0;
-  w.rec = (MiTri*)(base + o); o += mi_al(nt * sizeof(MiTri));
-  w.box = (double4*)(base + o); o += mi_al(nt * sizeof(double4));
-  w.state = (int*)(base + o); o += mi_al(nt * 4);
-  w.part = (MiBoxPart*)(base + o); o += mi_al((size_t)w.gprep * sizeof(MiBoxPart));
-  w.grid = (MiGrid*)(base + o); o += mi_al(sizeof(MiGrid));
-  w.used = (unsigned long long*)(base + o);                  // used and nall share one 256-byte slot, cleared together
-  w.nall = (int*)(base + o + 8); o += 256;
-  w.cnt = (int*)(base + o); o += mi_al(nc * 4);
-  w.start = (int*)(base + o); o += mi_al(nc * 4);
-  w.pairs = (int*)(base + o); o += mi_al((size_t)w.cap * 4);
-  w.all = (int*)(base + o); o += mi_al(nt * 4);
+  NmCarver c(base);
+  w.rec = c.take<MiTri>(nt);
+  w.box = c.take<double4>(nt);
+  w.state = c.take<int>(nt);
+  w.part = c.take<MiBoxPart>(w.gprep);
+  w.grid = c.take<MiGrid>(1);
+  w.used = c.take<unsigned long long>(1);                    // used and nall share one 256-byte slot, cleared together
+  w.nall = (int*)(w.used + 1);
+  w.cnt = c.take<int>(nc);
+  w.start = c.take<int>(nc);
+  w.pairs = c.take<int>((size_t)w.cap);
+  w.all = c.take<int>(nt);
   size_t tb = 0;
   rocprim::exclusive_scan(nullptr, tb, (int*)nullptr, (int*)nullptr, 0, nc, rocprim::plus<int>(), (hipStream_t)0);
   w.scan_bytes = tb;
-  w.scan_tmp = (void*)(base + o); o += mi_al(tb > 0 ? tb : 1);
-  w.total = o;
+  w.scan_tmp = c.take<char>(tb > 0 ? tb : 1);
+  w.total = c.total();
   return w;
 }
 
@@ -121,8 +122,9 @@ __device__ __forceinline__ bool mi_finite(double x) { return fabs(x) <= 1.797693
 __global__ void __launch_bounds__(kMiThreads) k_mi_prep(int T, int V, const double* __restrict__ verts, const int32_t* __restrict__ tris,
                                                         MiTri* __restrict__ rec, double4* __restrict__ box, int* __restrict__ state,
                                                         MiBoxPart* __restrict__ part) {
-  __shared__ double red[kMiThreads / 64][4];
-  double blo0 = INFINITY, blo1 = INFINITY, bhi0 = -INFINITY, bhi1 = -INFINITY;
+  constexpr int NW = kMiThreads / 64;
+  __shared__ double red[NW * 4];
+  double bb[4] = {INFINITY, INFINITY, -INFINITY, -INFINITY};      // lo x, lo y, hi x, hi y
   const int stride = gridDim.x * kMiThreads;
   for (int t = blockIdx.x * kMiThreads + threadIdx.x; t < T; t += stride) {
     const int ia = tris[3 * (size_t)t], ib = tris[3 * (size_t)t + 1], ic = tris[3 * (size_t)t + 2];
@@ -158,49 +160,35 @@ __global__ void __launch_bounds__(kMiThreads) k_mi_prep(int T, int V, const doub
     box[t] = bx;
     state[t] = boxed ? 0 : kTriAll;
     if (boxed) {               // the grid spans the boxed triangles' vertices (points and boxes beyond it clamp to its edge)
-      blo0 = fmin(blo0, fmin(fmin(a0, b0), c0)); blo1 = fmin(blo1, fmin(fmin(a1, b1), c1));
-      bhi0 = fmax(bhi0, fmax(fmax(a0, b0), c0)); bhi1 = fmax(bhi1, fmax(fmax(a1, b1), c1));
+      bb[0] = fmin(bb[0], fmin(fmin(a0, b0), c0)); bb[1] = fmin(bb[1], fmin(fmin(a1, b1), c1));
+      bb[2] = fmax(bb[2], fmax(fmax(a0, b0), c0)); bb[3] = fmax(bb[3], fmax(fmax(a1, b1), c1));
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    blo0 = fmin(blo0, __shfl_xor(blo0, o, 64)); blo1 = fmin(blo1, __shfl_xor(blo1, o, 64));
-    bhi0 = fmax(bhi0, __shfl_xor(bhi0, o, 64)); bhi1 = fmax(bhi1, __shfl_xor(bhi1, o, 64));
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[wave][0] = blo0; red[wave][1] = blo1; red[wave][2] = bhi0; red[wave][3] = bhi1; }
-  __syncthreads();
+  const auto tot = nm_block_reduce<NW, NmMinMax<2>>(bb, red);
   if (threadIdx.x == 0) {
     MiBoxPart p;
-    for (int j = 0; j < 2; ++j) {
-      p.lo[j] = fmin(fmin(red[0][j], red[1][j]), fmin(red[2][j], red[3][j]));
-      p.hi[j] = fmax(fmax(red[0][2 + j], red[1][2 + j]), fmax(red[2][2 + j], red[3][2 + j]));
-    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) { p.lo[j] = tot[j]; p.hi[j] = tot[2 + j]; }
     part[blockIdx.x] = p;
   }
 }
 
 // one workgroup: the mesh's xy box, then square cells within the budget (an axis shorter than the cell edge gets one cell)
 __global__ void __launch_bounds__(kMiThreads) k_mi_grid(int gprep, int cmax, const MiBoxPart* __restrict__ part, MiGrid* __restrict__ grid) {
-  __shared__ double red[kMiThreads / 64][4];
-  double lo0 = INFINITY, lo1 = INFINITY, hi0 = -INFINITY, hi1 = -INFINITY;
+  constexpr int NW = kMiThreads / 64;
+  __shared__ double red[NW * 4];
+  double bb[4] = {INFINITY, INFINITY, -INFINITY, -INFINITY};      // lo x, lo y, hi x, hi y
   for (int g = threadIdx.x; g < gprep; g += kMiThreads) {
     const MiBoxPart p = part[g];
-    lo0 = fmin(lo0, p.lo[0]); lo1 = fmin(lo1, p.lo[1]); hi0 = fmax(hi0, p.hi[0]); hi1 = fmax(hi1, p.hi[1]);
+    bb[0] = fmin(bb[0], p.lo[0]); bb[1] = fmin(bb[1], p.lo[1]); bb[2] = fmax(bb[2], p.hi[0]); bb[3] = fmax(bb[3], p.hi[1]);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo0 = fmin(lo0, __shfl_xor(lo0, o, 64)); lo1 = fmin(lo1, __shfl_xor(lo1, o, 64));
-    hi0 = fmax(hi0, __shfl_xor(hi0, o, 64)); hi1 = fmax(hi1, __shfl_xor(hi1, o, 64));
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[wave][0] = lo0; red[wave][1] = lo1; red[wave][2] = hi0; red[wave][3] = hi1; }
-  __syncthreads();
+  const auto tot = nm_block_reduce<NW, NmMinMax<2>>(bb, red);
   if (threadIdx.x != 0) return;
   double lo[2], e[2];
+#pragma unroll
   for (int j = 0; j < 2; ++j) {
-    lo[j] = fmin(fmin(red[0][j], red[1][j]), fmin(red[2][j], red[3][j]));
-    const double hi = fmax(fmax(red[0][2 + j], red[1][2 + j]), fmax(red[2][2 + j], red[3][2 + j]));
+    lo[j] = tot[j];
+    const double hi = tot[2 + j];
     e[j] = lo[j] <= hi ? hi - lo[j] : 0.0;                     // (no boxed triangle: one cell)
     if (!mi_finite(lo[j])) lo[j] = 0.0;
     if (!mi_finite(e[j])) e[j] = 0.0;                          // (a span beyond the fp64 range: one cell on that axis)
@@ -335,7 +323,7 @@ extern "C" int nm_points_in_mesh(int32_t n_verts, int32_t n_tris, int32_t n_poin
     NM_HIP_CHECK(hipMemsetAsync(inside_out, 0, (size_t)n_points, s));
     return NM_OK;
   }
-  const MiWs w = carve((char*)ws, n_tris);
+  const MiWs w = carve(ws, n_tris);
   NM_LAUNCH(k_mi_prep, dim3(w.gprep), dim3(kMiThreads), 0, s, n_tris, n_verts, verts, tris, w.rec, w.box, w.state, w.part);
   NM_LAUNCH_CHECK();
   NM_LAUNCH(k_mi_grid, dim3(1), dim3(kMiThreads), 0, s, w.gprep, w.cmax, (const MiBoxPart*)w.part, w.grid);

@@ -1,14 +1,16 @@
 // Image-quality metrics of experiments/evaluation.py: torchmetrics' PeakSignalNoiseRatio (the sum of squared errors) and
 // structural_similarity_index_measure (gaussian window 11 / sigma 1.5, k1 0.01, k2 0.03, data_range = the inputs' range) for a
-// batch of B images, with no host synchronisation and no atomics (two calls give identical bits).
+// batch of B images, with no host synchronisation and no atomics: every reduction is nm_reduce.h's, so two calls give identical bits.
 //   k_metrics_stats   pass 1: per image min / max of both inputs and the fp64 sum of squared errors, one partial per workgroup
-//   k_metrics_range   one workgroup: fixed-order finish of pass 1 -> sse_out[b] and c1 / c2 per image (own or batch-wide range)
+//   k_metrics_range   one workgroup: finish of pass 1 -> sse_out[b] and c1 / c2 per image (own or batch-wide range)
 //   k_metrics_ssim    pass 2: the SSIM map over the (H-10) x (W-10) windows lying inside the image, one fp64 partial per workgroup
-//   k_metrics_finish  one workgroup per image: fixed-order sum of its partials -> ssim_out[b]
+//   k_metrics_finish  one workgroup per image: sum of its partials -> ssim_out[b]
 // torchmetrics reflect-pads by 5, convolves without padding and crops 5 from each side of the map: what is left is exactly the
 // windows inside the image, so no padded pixel ever reaches the result and this file pads nothing.
 #include "nm_common.h"
+#include "nm_reduce.h"
 #include "nm_ssim.h"
+#include "nm_workspace.h"
 
 namespace {
 
@@ -37,10 +39,21 @@ static MetricDims metric_dims(int b, int c, int h, int w) {
 }
 
 // workspace: [stat partials B x 5 x g1][per image pmin, pmax, tmin, tmax, c1, c2: B x 6][ssim partials B x C x ty x tx], fp64
-static size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-static size_t ws_stat_bytes(const MetricDims& d) { return align256((size_t)d.b * kStatN * d.g1 * sizeof(double)); }
-static size_t ws_img_bytes(const MetricDims& d) { return align256((size_t)d.b * 6 * sizeof(double)); }
-static size_t ws_ssim_bytes(const MetricDims& d) { return align256((size_t)d.b * d.c * d.ty * d.tx * sizeof(double)); }
+struct MetricWs { double *part1, *stat, *part2; size_t total; };
+static MetricWs carve_metric_ws(void* base, const MetricDims& d) {
+  NmCarver c(base);
+  MetricWs w;
+  w.part1 = c.take<double>((size_t)d.b * kStatN * d.g1);
+  w.stat = c.take<double>((size_t)d.b * 6);
+  w.part2 = c.take<double>((size_t)d.b * d.c * d.ty * d.tx);
+  w.total = c.total();
+  return w;
+}
+
+// pass 1's five accumulators {pmin, tmin, pmax, tmax, sse} in one reduction
+struct StatOp {
+  __device__ __forceinline__ static double apply(int j, double a, double b) { return j == 4 ? a + b : NmMinMax<2>::apply(j, a, b); }
+};
 
 __device__ __forceinline__ void stat_elem(float p, float t, float& pmin, float& pmax, float& tmin, float& tmax, double& sse) {
   pmin = fminf(pmin, p); pmax = fmaxf(pmax, p);
@@ -53,7 +66,7 @@ __device__ __forceinline__ void stat_elem(float p, float t, float& pmin, float& 
 template <int V>
 __global__ void __launch_bounds__(kStatThreads) k_metrics_stats(MetricDims D, const float* __restrict__ preds,
                                                                const float* __restrict__ target, double* __restrict__ part) {
-  __shared__ double red[4][kStatN];
+  __shared__ double red[4 * kStatN];
   const int img = blockIdx.y;
   const float* P = preds + (size_t)img * D.n;
   const float* T = target + (size_t)img * D.n;
@@ -75,33 +88,24 @@ __global__ void __launch_bounds__(kStatThreads) k_metrics_stats(MetricDims D, co
     for (int64_t i = (int64_t)blockIdx.x * kStatThreads + threadIdx.x; i < D.n; i += stride)
       stat_elem(P[i], T[i], pmin, pmax, tmin, tmax, sse);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    pmin = fminf(pmin, __shfl_xor(pmin, o, 64)); pmax = fmaxf(pmax, __shfl_xor(pmax, o, 64));
-    tmin = fminf(tmin, __shfl_xor(tmin, o, 64)); tmax = fmaxf(tmax, __shfl_xor(tmax, o, 64));
-    sse += __shfl_xor(sse, o, 64);
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    red[wave][0] = pmin; red[wave][1] = pmax; red[wave][2] = tmin; red[wave][3] = tmax; red[wave][4] = sse;
-  }
-  __syncthreads();
+  const double st[kStatN] = {(double)pmin, (double)tmin, (double)pmax, (double)tmax, sse};      // (the partials are fp64)
+  const auto tot = nm_block_reduce<4, StatOp>(st, red);
   if (threadIdx.x == 0) {
     double* q = part + (size_t)img * kStatN * D.g1 + blockIdx.x;
-    q[0 * D.g1] = fmin(fmin(red[0][0], red[1][0]), fmin(red[2][0], red[3][0]));
-    q[1 * D.g1] = fmax(fmax(red[0][1], red[1][1]), fmax(red[2][1], red[3][1]));
-    q[2 * D.g1] = fmin(fmin(red[0][2], red[1][2]), fmin(red[2][2], red[3][2]));
-    q[3 * D.g1] = fmax(fmax(red[0][3], red[1][3]), fmax(red[2][3], red[3][3]));
-    q[4 * D.g1] = ((red[0][4] + red[1][4]) + red[2][4]) + red[3][4];
+    q[0 * D.g1] = tot[0];
+    q[1 * D.g1] = tot[2];
+    q[2 * D.g1] = tot[1];
+    q[3 * D.g1] = tot[3];
+    q[4 * D.g1] = tot[4];
   }
 }
 
-// One workgroup of 256.  Wave w finishes images w, w + 4, ... (lanes over the g1 partials, then a fixed shuffle tree):
+// One workgroup of 256.  Wave w finishes images w, w + 4, ... (lanes over the g1 partials, then the wave reduce):
 // sse_out[b] and the image's min / max.  Then c1 = (0.01 dr)^2, c2 = (0.03 dr)^2 per image, dr = max(pmax - pmin, tmax - tmin)
 // over that image (per_image) or over the whole batch (torchmetrics on a batched call).
 __global__ void __launch_bounds__(256) k_metrics_range(MetricDims D, int per_image, const double* __restrict__ part,
                                                        double* __restrict__ stat, double* __restrict__ sse_out) {
-  __shared__ double red[4][4];
+  __shared__ double red[4 * 4];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int img = wave; img < D.b; img += 4) {
     const double* q = part + (size_t)img * kStatN * D.g1;
@@ -111,12 +115,9 @@ __global__ void __launch_bounds__(256) k_metrics_range(MetricDims D, int per_ima
       tmin = fmin(tmin, q[2 * D.g1 + j]); tmax = fmax(tmax, q[3 * D.g1 + j]);
       sse += q[4 * D.g1 + j];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      pmin = fmin(pmin, __shfl_xor(pmin, o, 64)); pmax = fmax(pmax, __shfl_xor(pmax, o, 64));
-      tmin = fmin(tmin, __shfl_xor(tmin, o, 64)); tmax = fmax(tmax, __shfl_xor(tmax, o, 64));
-      sse += __shfl_xor(sse, o, 64);
-    }
+    pmin = nm_wave_reduce<NmMin>(pmin); pmax = nm_wave_reduce<NmMax>(pmax);
+    tmin = nm_wave_reduce<NmMin>(tmin); tmax = nm_wave_reduce<NmMax>(tmax);
+    sse = nm_wave_reduce<NmSum>(sse);
     if (lane == 0) {
       double* s = stat + (size_t)img * 6;
       s[0] = pmin; s[1] = pmax; s[2] = tmin; s[3] = tmax;
@@ -126,21 +127,13 @@ __global__ void __launch_bounds__(256) k_metrics_range(MetricDims D, int per_ima
   __syncthreads();                 // (also orders the global writes above for the reads below: one workgroup)
   double bmin_p = INFINITY, bmax_p = -INFINITY, bmin_t = INFINITY, bmax_t = -INFINITY;
   if (!per_image) {
+    double r[4] = {INFINITY, INFINITY, -INFINITY, -INFINITY};      // pmin, tmin, pmax, tmax
     for (int img = threadIdx.x; img < D.b; img += blockDim.x) {
       const double* s = stat + (size_t)img * 6;
-      bmin_p = fmin(bmin_p, s[0]); bmax_p = fmax(bmax_p, s[1]); bmin_t = fmin(bmin_t, s[2]); bmax_t = fmax(bmax_t, s[3]);
+      r[0] = fmin(r[0], s[0]); r[2] = fmax(r[2], s[1]); r[1] = fmin(r[1], s[2]); r[3] = fmax(r[3], s[3]);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      bmin_p = fmin(bmin_p, __shfl_xor(bmin_p, o, 64)); bmax_p = fmax(bmax_p, __shfl_xor(bmax_p, o, 64));
-      bmin_t = fmin(bmin_t, __shfl_xor(bmin_t, o, 64)); bmax_t = fmax(bmax_t, __shfl_xor(bmax_t, o, 64));
-    }
-    if (lane == 0) { red[wave][0] = bmin_p; red[wave][1] = bmax_p; red[wave][2] = bmin_t; red[wave][3] = bmax_t; }
-    __syncthreads();
-    bmin_p = fmin(fmin(red[0][0], red[1][0]), fmin(red[2][0], red[3][0]));
-    bmax_p = fmax(fmax(red[0][1], red[1][1]), fmax(red[2][1], red[3][1]));
-    bmin_t = fmin(fmin(red[0][2], red[1][2]), fmin(red[2][2], red[3][2]));
-    bmax_t = fmax(fmax(red[0][3], red[1][3]), fmax(red[2][3], red[3][3]));
+    const auto tot = nm_block_reduce<4, NmMinMax<2>>(r, red);
+    bmin_p = tot[0]; bmin_t = tot[1]; bmax_p = tot[2]; bmax_t = tot[3];
   }
   for (int img = threadIdx.x; img < D.b; img += blockDim.x) {
     double* s = stat + (size_t)img * 6;
@@ -204,40 +197,24 @@ __global__ void __launch_bounds__(kSsimThreads) k_metrics_ssim(MetricDims D, Win
     const double upper = 2.0 * s12 + c2, lower = (s1 + s2) + c2;
     ssum += ((2.0 * mu12 + c1) * upper) / (((mu1_sq + mu2_sq) + c1) * lower);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) ssum += __shfl_xor(ssum, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ssum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double acc = red[0];
-#pragma unroll
-    for (int i = 1; i < kSsimWaves; ++i) acc += red[i];
-    part[((size_t)plane_id * D.ty + by) * D.tx + bx] = acc;
-  }
+  ssum = nm_block_reduce<kSsimWaves, NmSum>(ssum, red);
+  if (threadIdx.x == 0) part[((size_t)plane_id * D.ty + by) * D.tx + bx] = ssum;
 }
 
-// grid (B): ssim_out[b] = (fixed-order sum of image b's C * ty * tx partials) / (C (H - 10) (W - 10))
+// grid (B): ssim_out[b] = (sum of image b's C * ty * tx partials) / (C (H - 10) (W - 10))
 __global__ void __launch_bounds__(256) k_metrics_finish(MetricDims D, const double* __restrict__ part, double* __restrict__ ssim_out) {
   __shared__ double red[4];
   const int img = blockIdx.x;
   const int np = D.c * D.ty * D.tx;
-  const double* q = part + (size_t)img * np;
-  double acc = 0.0;
-  for (int j = threadIdx.x; j < np; j += blockDim.x) acc += q[j];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    ssim_out[img] = (((red[0] + red[1]) + red[2]) + red[3]) / ((double)D.c * (double)(D.h - 2 * kR) * (double)(D.w - 2 * kR));
+  const double sum = nm_block_sum_partials<4, 1>(part + (size_t)img * np, np, 1, red)[0];
+  if (threadIdx.x == 0) ssim_out[img] = sum / ((double)D.c * (double)(D.h - 2 * kR) * (double)(D.w - 2 * kR));
 }
 
 }  // namespace
 
 extern "C" size_t nm_image_metrics_workspace(int32_t b, int32_t c, int32_t h, int32_t w) {
   if (b <= 0 || c <= 0 || h < kWin || w < kWin) return 0;
-  const MetricDims d = metric_dims(b, c, h, w);
-  return ws_stat_bytes(d) + ws_img_bytes(d) + ws_ssim_bytes(d);
+  return carve_metric_ws(nullptr, metric_dims(b, c, h, w)).total;
 }
 
 extern "C" int nm_image_metrics(int32_t b, int32_t c, int32_t h, int32_t w, const float* preds, const float* target,
@@ -249,9 +226,8 @@ extern "C" int nm_image_metrics(int32_t b, int32_t c, int32_t h, int32_t w, cons
   NM_REQUIRE(preds && target && sse_out && workspace, "null pointer");
   const MetricDims D = metric_dims(b, c, h, w);
   NM_REQUIRE(workspace_bytes >= nm_image_metrics_workspace(b, c, h, w), "workspace too small (nm_image_metrics_workspace)");
-  double* part1 = (double*)workspace;
-  double* stat = (double*)((char*)workspace + ws_stat_bytes(D));
-  double* part2 = (double*)((char*)workspace + ws_stat_bytes(D) + ws_img_bytes(D));
+  const MetricWs ws = carve_metric_ws(workspace, D);
+  double *part1 = ws.part1, *stat = ws.stat, *part2 = ws.part2;
   const hipStream_t s = (hipStream_t)stream;
   const bool vec4 = D.n % 4 == 0 && ((uintptr_t)preds | (uintptr_t)target) % 16 == 0;
   if (vec4)

@@ -13,11 +13,13 @@
 // cell and stops once its best squared distance is at most a lower bound on the squared distance to every unvisited cell:
 // the distance to the slab beyond each face of the visited block, inside the targets' box (valid for queries outside it).
 // Distances are fp64 from the fp32 coordinates, the winner is the lexicographic minimum of (distance^2, target index), so the
-// result does not depend on the order of points inside a cell (nor on the atomics' ranks).  The per-item means are fixed-order
-// fp64 sums over the queries in their ORIGINAL order (k_nn_mean_part, k_nn_mean_finish): two calls give identical bits.
+// result does not depend on the order of points inside a cell (nor on the atomics' ranks).  The per-item means are fp64 sums in
+// the fixed order of nm_reduce.h over the queries in their ORIGINAL order (k_nn_mean_part, k_nn_mean_finish).
 // The k-NN search (k_nn_search_k, 1 <= k <= 16: nm_knn, and nm_knn_mean_dist2 = simple_knn's distCUDA2 at k = 3) is the same
 // walk with a k-best list per thread in registers; it stops on the k-th best instead of the best.
 #include "nm_common.h"
+#include "nm_reduce.h"
+#include "nm_workspace.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -44,7 +46,6 @@ struct NnGrid {          // one per (cloud, item), written by k_nn_grid
   int bad;               // the cloud holds a NaN / Inf coordinate in this item
 };
 
-static inline size_t nn_al(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline int nn_box_blocks(int p) {
   const int g = nm_div_up(p, kNnThreads * 8);
   return g < 1 ? 1 : (g > kBoxMaxBlocks ? kBoxMaxBlocks : g);
@@ -67,26 +68,23 @@ struct NnBin {
   float4* sorted;    // B * P
   void* scan_tmp;
   size_t scan_bytes;
-  size_t total;
 };
 
-static NnBin carve_bin(char* base, int b, int p) {
+static NnBin carve_bin(NmCarver& c, int b, int p) {
   NnBin w;
   w.b = b; w.p = p; w.cmax = nn_cell_budget(p); w.gbox = nn_box_blocks(p);
   const size_t np = (size_t)b * p, nc = (size_t)b * w.cmax + 1;
-  size_t o = 0;
-  w.part = (NnBoxPart*)(base + o); o += nn_al((size_t)b * w.gbox * sizeof(NnBoxPart));
-  w.grid = (NnGrid*)(base + o); o += nn_al((size_t)b * sizeof(NnGrid));
-  w.cnt = (int*)(base + o); o += nn_al(nc * 4);
-  w.start = (int*)(base + o); o += nn_al(nc * 4);
-  w.key = (int*)(base + o); o += nn_al(np * 4);
-  w.rank = (int*)(base + o); o += nn_al(np * 4);
-  w.sorted = (float4*)(base + o); o += nn_al(np * sizeof(float4));
+  w.part = c.take<NnBoxPart>((size_t)b * w.gbox);
+  w.grid = c.take<NnGrid>(b);
+  w.cnt = c.take<int>(nc);
+  w.start = c.take<int>(nc);
+  w.key = c.take<int>(np);          // key + rank: nm_chamfer may reuse the pair as B * P int64
+  w.rank = c.take<int>(np);
+  w.sorted = c.take<float4>(np);
   size_t tb = 0;
   rocprim::exclusive_scan(nullptr, tb, (int*)nullptr, (int*)nullptr, 0, nc, rocprim::plus<int>(), (hipStream_t)0);
   w.scan_bytes = tb;
-  w.scan_tmp = (void*)(base + o); o += nn_al(tb > 0 ? tb : 1);
-  w.total = o;
+  w.scan_tmp = c.take<char>(tb > 0 ? tb : 1);
   return w;
 }
 
@@ -96,40 +94,29 @@ __device__ __forceinline__ bool nn_finite3(float x, float y, float z) {
 
 // grid (gbox, B): partial box of the finite points of item blockIdx.y, and the count of points with a non-finite coordinate
 __global__ void __launch_bounds__(kNnThreads) k_nn_box(int P, int gbox, const float* __restrict__ pts, NnBoxPart* __restrict__ part) {
-  __shared__ float red[kNnThreads / 64][6];
-  __shared__ int redb[kNnThreads / 64];
+  constexpr int NW = kNnThreads / 64;
+  __shared__ float red[NW * 6];
+  __shared__ int rbad[NW];
   const int item = blockIdx.y;
   const float* X = pts + (size_t)item * P * 3;
-  float lo0 = INFINITY, lo1 = INFINITY, lo2 = INFINITY, hi0 = -INFINITY, hi1 = -INFINITY, hi2 = -INFINITY;
+  float bb[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};      // lo[3], hi[3]
   int bad = 0;
   for (int i = blockIdx.x * kNnThreads + threadIdx.x; i < P; i += gbox * kNnThreads) {
     const float x = X[3 * (size_t)i], y = X[3 * (size_t)i + 1], z = X[3 * (size_t)i + 2];
     if (nn_finite3(x, y, z)) {
-      lo0 = fminf(lo0, x); lo1 = fminf(lo1, y); lo2 = fminf(lo2, z);
-      hi0 = fmaxf(hi0, x); hi1 = fmaxf(hi1, y); hi2 = fmaxf(hi2, z);
+      bb[0] = fminf(bb[0], x); bb[1] = fminf(bb[1], y); bb[2] = fminf(bb[2], z);
+      bb[3] = fmaxf(bb[3], x); bb[4] = fmaxf(bb[4], y); bb[5] = fmaxf(bb[5], z);
     } else {
       ++bad;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo0 = fminf(lo0, __shfl_xor(lo0, o, 64)); lo1 = fminf(lo1, __shfl_xor(lo1, o, 64)); lo2 = fminf(lo2, __shfl_xor(lo2, o, 64));
-    hi0 = fmaxf(hi0, __shfl_xor(hi0, o, 64)); hi1 = fmaxf(hi1, __shfl_xor(hi1, o, 64)); hi2 = fmaxf(hi2, __shfl_xor(hi2, o, 64));
-    bad += __shfl_xor(bad, o, 64);
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    red[wave][0] = lo0; red[wave][1] = lo1; red[wave][2] = lo2; red[wave][3] = hi0; red[wave][4] = hi1; red[wave][5] = hi2;
-    redb[wave] = bad;
-  }
-  __syncthreads();
+  const auto tot = nm_block_reduce<NW, NmMinMax<3>>(bb, red);
+  bad = nm_block_reduce<NW, NmSum>(bad, rbad);
   if (threadIdx.x == 0) {
     NnBoxPart r;
-    for (int k = 0; k < 3; ++k) {
-      r.lo[k] = fminf(fminf(red[0][k], red[1][k]), fminf(red[2][k], red[3][k]));
-      r.hi[k] = fmaxf(fmaxf(red[0][3 + k], red[1][3 + k]), fmaxf(red[2][3 + k], red[3][3 + k]));
-    }
-    r.bad = redb[0] + redb[1] + redb[2] + redb[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { r.lo[k] = tot[k]; r.hi[k] = tot[3 + k]; }
+    r.bad = bad;
     r.pad = 0;
     part[(size_t)item * gbox + blockIdx.x] = r;
   }
@@ -399,11 +386,8 @@ __global__ void __launch_bounds__(kNnThreads) k_nn_mean_part(int N, int gmean, c
   const double* D = d2 + (size_t)item * N;
   double acc = 0.0;
   for (int i = blockIdx.x * kNnThreads + threadIdx.x; i < N; i += gmean * kNnThreads) acc += D[i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[(size_t)item * gmean + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+  acc = nm_block_reduce<kNnThreads / 64, NmSum>(acc, red);
+  if (threadIdx.x == 0) part[(size_t)item * gmean + blockIdx.x] = acc;
 }
 
 // one workgroup: wave w finishes items w, w + 4, ...  mean = sum / N, NaN where either cloud of the item is non-finite
@@ -414,8 +398,7 @@ __global__ void __launch_bounds__(kNnThreads) k_nn_mean_finish(int B, int N, int
   for (int item = wave; item < B; item += kNnThreads / 64) {
     double acc = 0.0;
     for (int j = lane; j < gmean; j += 64) acc += part[(size_t)item * gmean + j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    acc = nm_wave_reduce<NmSum>(acc);
     if (lane == 0) out[item] = (ga[item].bad || gb[item].bad) ? (double)NAN : acc / (double)N;
   }
 }
@@ -480,18 +463,15 @@ static bool nn_sizes_ok(int32_t b, int32_t n1, int32_t n2) {
 struct ChamferWs {
   NnBin a, b;
   double *d2a, *d2b, *part;
-  size_t total;
 };
 
-static ChamferWs carve_chamfer(char* base, int b, int n1, int n2) {
+static ChamferWs carve_chamfer(NmCarver& c, int b, int n1, int n2) {
   ChamferWs w;
-  size_t o = 0;
-  w.a = carve_bin(base + o, b, n1); o += w.a.total;
-  w.b = carve_bin(base + o, b, n2); o += w.b.total;
-  w.d2a = (double*)(base + o); o += nn_al((size_t)b * n1 * sizeof(double));
-  w.d2b = (double*)(base + o); o += nn_al((size_t)b * n2 * sizeof(double));
-  w.part = (double*)(base + o); o += nn_al((size_t)b * (nn_mean_blocks(n1) + nn_mean_blocks(n2)) * sizeof(double));
-  w.total = o;
+  w.a = carve_bin(c, b, n1);
+  w.b = carve_bin(c, b, n2);
+  w.d2a = c.take<double>((size_t)b * n1);
+  w.d2b = c.take<double>((size_t)b * n2);
+  w.part = c.take<double>((size_t)b * (nn_mean_blocks(n1) + nn_mean_blocks(n2)));
   return w;
 }
 
@@ -499,8 +479,10 @@ static ChamferWs carve_chamfer(char* base, int b, int n1, int n2) {
 
 extern "C" size_t nm_nn_workspace(int32_t b, int32_t n_query, int32_t n_target) {
   if (!nn_sizes_ok(b, n_query, n_target)) return 0;
-  const NnBin q = carve_bin(nullptr, b, n_query);
-  return q.total + carve_bin(nullptr, b, n_target).total;
+  NmCarver c(nullptr);
+  carve_bin(c, b, n_query);
+  carve_bin(c, b, n_target);
+  return c.total();
 }
 
 extern "C" int nm_nearest_neighbors(int32_t b, int32_t n_query, int32_t n_target, const float* query, const float* target,
@@ -511,8 +493,9 @@ extern "C" int nm_nearest_neighbors(int32_t b, int32_t n_query, int32_t n_target
   NM_REQUIRE(query && target && idx_out && ws, "null pointer");
   NM_REQUIRE(ws_bytes >= nm_nn_workspace(b, n_query, n_target), "workspace too small (nm_nn_workspace)");
   const hipStream_t s = (hipStream_t)stream;
-  const NnBin q = carve_bin((char*)ws, b, n_query);
-  const NnBin t = carve_bin((char*)ws + q.total, b, n_target);
+  NmCarver c(ws);
+  const NnBin q = carve_bin(c, b, n_query);
+  const NnBin t = carve_bin(c, b, n_target);
   int rc;
   if ((rc = nn_bin(q, query, s)) != NM_OK) return rc;
   if ((rc = nn_bin(t, target, s)) != NM_OK) return rc;
@@ -535,8 +518,9 @@ extern "C" int nm_knn(int32_t b, int32_t n_query, int32_t n_target, int32_t k, i
   NM_REQUIRE(query && target && idx_out && ws, "null pointer");
   NM_REQUIRE(ws_bytes >= nm_knn_workspace(b, n_query, n_target, k), "workspace too small (nm_knn_workspace)");
   const hipStream_t s = (hipStream_t)stream;
-  const NnBin q = carve_bin((char*)ws, b, n_query);
-  const NnBin t = carve_bin((char*)ws + q.total, b, n_target);
+  NmCarver c(ws);
+  const NnBin q = carve_bin(c, b, n_query);
+  const NnBin t = carve_bin(c, b, n_target);
   int rc;
   if ((rc = nn_bin(q, query, s)) != NM_OK) return rc;
   if ((rc = nn_bin(t, target, s)) != NM_OK) return rc;
@@ -545,7 +529,9 @@ extern "C" int nm_knn(int32_t b, int32_t n_query, int32_t n_target, int32_t k, i
 
 extern "C" size_t nm_knn_mean_dist2_workspace(int32_t n) {
   if (!nn_sizes_ok(1, n, n)) return 0;
-  return carve_bin(nullptr, 1, n).total;
+  NmCarver c(nullptr);
+  carve_bin(c, 1, n);
+  return c.total();
 }
 
 extern "C" int nm_knn_mean_dist2(int32_t n, const float* points, int32_t k, float* out, void* ws, size_t ws_bytes, void* stream) {
@@ -555,15 +541,18 @@ extern "C" int nm_knn_mean_dist2(int32_t n, const float* points, int32_t k, floa
   NM_REQUIRE(points && out && ws, "null pointer");
   NM_REQUIRE(ws_bytes >= nm_knn_mean_dist2_workspace(n), "workspace too small (nm_knn_mean_dist2_workspace)");
   const hipStream_t s = (hipStream_t)stream;
-  const NnBin c = carve_bin((char*)ws, 1, n);           // the cloud is binned once: it is both the queries and the targets
+  NmCarver c(ws);
+  const NnBin cloud = carve_bin(c, 1, n);               // the cloud is binned once: it is both the queries and the targets
   int rc;
-  if ((rc = nn_bin(c, points, s)) != NM_OK) return rc;
-  return nn_search_k(c, c, k, 1, nullptr, nullptr, out, s);
+  if ((rc = nn_bin(cloud, points, s)) != NM_OK) return rc;
+  return nn_search_k(cloud, cloud, k, 1, nullptr, nullptr, out, s);
 }
 
 extern "C" size_t nm_chamfer_workspace(int32_t b, int32_t n1, int32_t n2) {
   if (!nn_sizes_ok(b, n1, n2)) return 0;
-  return carve_chamfer(nullptr, b, n1, n2).total;
+  NmCarver c(nullptr);
+  carve_chamfer(c, b, n1, n2);
+  return c.total();
 }
 
 extern "C" int nm_chamfer(int32_t b, int32_t n1, int32_t n2, const float* p1, const float* p2, double* cd12_out, double* cd21_out,
@@ -574,7 +563,8 @@ extern "C" int nm_chamfer(int32_t b, int32_t n1, int32_t n2, const float* p1, co
   NM_REQUIRE(p1 && p2 && cd12_out && cd21_out && ws, "null pointer");
   NM_REQUIRE(ws_bytes >= nm_chamfer_workspace(b, n1, n2), "workspace too small (nm_chamfer_workspace)");
   const hipStream_t s = (hipStream_t)stream;
-  const ChamferWs w = carve_chamfer((char*)ws, b, n1, n2);
+  NmCarver c(ws);
+  const ChamferWs w = carve_chamfer(c, b, n1, n2);
   // without caller arrays the indices go to the (then unused) key arrays' space: B * n int64 = the key + rank arrays
   int64_t* i12 = idx12 ? idx12 : (int64_t*)w.a.key;
   int64_t* i21 = idx21 ? idx21 : (int64_t*)w.b.key;

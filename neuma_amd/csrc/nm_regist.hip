@@ -1,11 +1,13 @@
 // Gaussian registration (experiments/regist.py): the per-Gaussian transform + covariance build and its adjoint reduced to
 // 17 scalars, and the SSIM loss with its adjoint.
 //   nm_regist_apply     Register.forward (modules/tune/regist/register.py) + general_utils.py:93-139, one thread per Gaussian
-//   nm_regist_backward  its adjoint; per-block fp64 partials, then one fixed-order block: bitwise reproducible, no atomics
+//   nm_regist_backward  its adjoint; per-block fp64 partials, then one workgroup sums them (nm_reduce.h): no atomics
 //   nm_ssim_loss        modules/d3gs/utils/loss_utils.py:26-66 fused with its adjoint (separable 11-tap passes over LDS tiles)
 #include "nm_common.h"
 #include "nm_gaussian.h"
+#include "nm_reduce.h"
 #include "nm_ssim.h"
+#include "nm_workspace.h"
 
 namespace {
 
@@ -102,27 +104,6 @@ static int regist_blocks(int K) {
   return b < 1 ? 1 : (b > kRegMaxBlocks ? kRegMaxBlocks : b);
 }
 
-// block-wide fixed-order sum of kRegN doubles (valid in thread 0's `out`)
-__device__ __forceinline__ void block_sum17(double* acc, double* sh /* [4][kRegN] */) {
-#pragma unroll
-  for (int j = 0; j < kRegN; ++j) {
-    double v = acc[j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    acc[j] = v;
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int j = 0; j < kRegN; ++j) sh[wave * kRegN + j] = acc[j];
-  }
-  __syncthreads();
-  if (threadIdx.x < kRegN) {
-    const int j = threadIdx.x;
-    acc[0] = ((sh[j] + sh[kRegN + j]) + sh[2 * kRegN + j]) + sh[3 * kRegN + j];
-  }
-}
-
 __global__ void __launch_bounds__(kRegThreads) k_regist_bwd(int K, const float* __restrict__ xyz, const float* __restrict__ ls,
                                                             const float* __restrict__ rot, const float* __restrict__ params,
                                                             float mod, const float* __restrict__ gm, const float* __restrict__ gc,
@@ -163,21 +144,15 @@ __global__ void __launch_bounds__(kRegThreads) k_regist_bwd(int K, const float* 
     acc[11] += (double)(-y0 * dqm[0] + z0 * dqm[1] + w0 * dqm[2] - x0 * dqm[3]);
     acc[12] += (double)(-z0 * dqm[0] - y0 * dqm[1] + x0 * dqm[2] + w0 * dqm[3]);
   }
-  block_sum17(acc, sh);
-  if (threadIdx.x < kRegN) part[(size_t)blockIdx.x * kRegN + threadIdx.x] = acc[0];
+  const auto tot = nm_block_reduce<4, NmSum>(acc, sh);
+  if (threadIdx.x < kRegN) part[(size_t)blockIdx.x * kRegN + threadIdx.x] = tot[threadIdx.x];
 }
 
-// one block: the partials of every scalar in a fixed order, then out[j] += sum
+// one block: the partials of every scalar, then out[j] += sum
 __global__ void __launch_bounds__(256) k_regist_reduce(int nb, const double* __restrict__ part, float* __restrict__ out) {
   __shared__ double sh[4 * kRegN];
-  double acc[kRegN];
-#pragma unroll
-  for (int j = 0; j < kRegN; ++j) acc[j] = 0.0;
-  for (int b = threadIdx.x; b < nb; b += blockDim.x)
-#pragma unroll
-    for (int j = 0; j < kRegN; ++j) acc[j] += part[(size_t)b * kRegN + j];
-  block_sum17(acc, sh);
-  if (threadIdx.x < kRegN) out[threadIdx.x] = (float)((double)out[threadIdx.x] + acc[0]);
+  const auto tot = nm_block_sum_partials<4, kRegN>(part, nb, kRegN, sh);
+  if (threadIdx.x < kRegN) out[threadIdx.x] = (float)((double)out[threadIdx.x] + tot[threadIdx.x]);
 }
 
 // ---------------------------------------------------------------- SSIM
@@ -197,7 +172,8 @@ static SsimDims ssim_dims(int h, int w) {
   return d;
 }
 
-static size_t ssim_part_bytes(const SsimDims& d) { return ((size_t)d.nblk * sizeof(double) + 255) / 256 * 256; }
+// workspace: [part: one double per k_ssim_fwd workgroup, padded][maps: 9 h w floats, not padded]
+static size_t ssim_part_bytes(const SsimDims& d) { return nm_align256((size_t)d.nblk * sizeof(double)); }
 
 // Pass 1: five blurred moments per pixel, the SSIM map, its per-block fp64 sum and (maps != NULL) the three coefficient maps
 // a = dS/dmu1, b = dS/dE[x^2], c = dS/dE[xy].
@@ -256,24 +232,16 @@ __global__ void __launch_bounds__(256) k_ssim_fwd(SsimDims D, Window W, const fl
       maps[6 * plane + p] = 2.f * S / A2;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) ssum += __shfl_xor(ssum, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ssum;
-  __syncthreads();
-  if (threadIdx.x == 0) part[((size_t)ch * D.ty + by) * D.tx + bx] = ((red[0] + red[1]) + red[2]) + red[3];
+  ssum = nm_block_reduce<4, NmSum>(ssum, red);
+  if (threadIdx.x == 0) part[((size_t)ch * D.ty + by) * D.tx + bx] = ssum;
 }
 
-// fixed-order sum of the pass-1 partials by one workgroup: *loss += weight (1 - mean S)
+// sum of the pass-1 partials by one workgroup: *loss += weight (1 - mean S)
 __device__ void ssim_finish(const SsimDims& D, const double* __restrict__ part, float weight, float* __restrict__ loss) {
   __shared__ double red[4];
-  double acc = 0.0;
-  for (int b = threadIdx.x; b < D.nblk; b += blockDim.x) acc += part[b];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
+  const double sum = nm_block_sum_partials<4, 1>(part, D.nblk, 1, red)[0];
   if (threadIdx.x == 0) {
-    const double mean = (((red[0] + red[1]) + red[2]) + red[3]) / (3.0 * (double)D.h * (double)D.w);
+    const double mean = sum / (3.0 * (double)D.h * (double)D.w);
     *loss = (float)((double)*loss + (double)weight * (1.0 - mean));
   }
 }
@@ -368,8 +336,7 @@ extern "C" int nm_regist_backward(int32_t k, const float* xyz, const float* log_
 
 extern "C" size_t nm_ssim_workspace(int32_t h, int32_t w) {
   if (h <= 0 || w <= 0) return 0;
-  const SsimDims d = ssim_dims(h, w);
-  return ssim_part_bytes(d) + (size_t)9 * h * w * sizeof(float);
+  return ssim_part_bytes(ssim_dims(h, w)) + (size_t)9 * h * w * sizeof(float);
 }
 
 extern "C" int nm_ssim_loss(float weight, int32_t h, int32_t w, const float* img, const float* gt, float* loss_out, float* dL_dimg,

@@ -7,6 +7,7 @@
 // No float atomics anywhere: two calls give the same bits.  A thread owns the same four floats whether it loads them as one
 // float4 (16-byte aligned bases) or one by one, and adds them in the same order, so both paths give the same bits too.
 #include "nm_common.h"
+#include "nm_reduce.h"
 
 namespace {
 
@@ -19,31 +20,18 @@ static int state_blocks(int64_t items) {
 }
 static size_t state_part_bytes() { return (size_t)kStMaxBlocks * 2 * sizeof(double); }
 
-// block-wide fixed-order sum (wave shuffles, then the four wave sums through LDS); valid in every thread
-template <typename T>
-__device__ __forceinline__ T state_block_sum(T v, T* sh /* [4] */) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();      // (sh may still be read from an earlier sum)
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
 __global__ void __launch_bounds__(kStThreads) k_state_count(int n, const uint8_t* __restrict__ mask, uint32_t* __restrict__ cnt) {
   __shared__ uint32_t sh[4];
   uint32_t c = 0;
   for (int64_t i = (int64_t)blockIdx.x * kStThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kStThreads) c += mask[i] != 0;
-  c = state_block_sum(c, sh);
+  c = nm_block_reduce<4, NmSum>(c, sh);
   if (threadIdx.x == 0) cnt[blockIdx.x] = c;
 }
 
 // rows kept: n without a mask, else the count partials (integers: exact in any order)
 __device__ __forceinline__ uint32_t state_kept(int n, int nbc, const uint32_t* __restrict__ cnt, uint32_t* sh) {
   if (!cnt) return (uint32_t)n;
-  uint32_t c = 0;
-  for (int b = threadIdx.x; b < nbc; b += kStThreads) c += cnt[b];
-  return state_block_sum(c, sh);
+  return nm_block_sum_partials<4, 1>(cnt, nbc, 1, sh)[0];
 }
 
 // One of the two terms over `total` = 3 n floats.  Thread t of the grid owns floats [4 q, 4 q + 4) for q = t, t + grid, ...
@@ -127,8 +115,8 @@ __global__ void __launch_bounds__(kStThreads) k_state_loss(int n, int kind, floa
   } else if (gv) {
     state_zero(total, vec_v != 0, gv);
   }
-  ax = state_block_sum(ax, shd);
-  av = state_block_sum(av, shd);
+  ax = nm_block_reduce<4, NmSum>(ax, shd);
+  av = nm_block_reduce<4, NmSum>(av, shd);
   if (threadIdx.x == 0) {
     part[2 * blockIdx.x] = ax;
     part[2 * blockIdx.x + 1] = av;
@@ -141,13 +129,8 @@ __global__ void __launch_bounds__(kStThreads) k_state_finish(int n, int nb, cons
   __shared__ uint32_t shc[4];
   __shared__ double shd[4];
   const uint32_t m = state_kept(n, nbc, cnt, shc);
-  double ax = 0.0, av = 0.0;
-  for (int b = threadIdx.x; b < nb; b += kStThreads) {
-    ax += part[2 * b];
-    av += part[2 * b + 1];
-  }
-  ax = state_block_sum(ax, shd);
-  av = state_block_sum(av, shd);
+  const double ax = nm_block_sum_partials<4, 1>(part, nb, 2, shd)[0];
+  const double av = nm_block_sum_partials<4, 1>(part + 1, nb, 2, shd)[0];
   if (threadIdx.x == 0) {
     const double inv = m ? 1.0 / (3.0 * (double)m) : 0.0;
     const double tx = ax * inv, tv = has_v ? av * inv : 0.0;

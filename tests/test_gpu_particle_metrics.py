@@ -123,6 +123,49 @@ def test_two_calls_give_identical_bits():
         assert measured(int((u.view(torch.int64) != v.view(torch.int64)).sum()), "bit differences between two calls") <= 0
 
 
+def _xor_tree(v):
+    """the wave reduce of csrc/nm_reduce.h over the last axis (64 lanes): v = v + v[lane ^ o], o = 32 .. 1"""
+    lane = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        v = v + v[..., lane ^ o]
+    return v
+
+
+def _fixed_order_mean(d2):
+    """k_nn_mean_part + k_nn_mean_finish of csrc/nm_nn.hip on one item's d2 (N,), one IEEE fp64 operation at a time"""
+    n = len(d2)
+    gm = min(max(-(-n // 4096), 1), 64)
+    stride = gm * 256
+    rounds = -(-n // stride)
+    x = np.zeros(rounds * stride)                 # (a thread past the end adds nothing; d2 >= 0, so + 0.0 changes no bit)
+    x[:n] = d2
+    acc = np.zeros(stride)                        # thread t of block b sums i = b * 256 + t, + gm * 256, ... in turn
+    for k in range(rounds):
+        acc = acc + x[k * stride:(k + 1) * stride]
+    w = _xor_tree(acc.reshape(gm, 4, 64))[..., 0]
+    part = ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]      # the waves left to right
+    lanes = np.zeros(64)                          # finish: lane j sums partials j, j + 64, ... (gm <= 64: at most one)
+    lanes[:gm] = part
+    return _xor_tree(lanes)[0] / np.float64(n)
+
+
+@pytest.mark.parametrize("n", [1, 255, 257, 4097, 64 * 4096 + 3])
+def test_chamfer_means_are_the_documented_fixed_order_sum(n):
+    """n: one lane; fewer than 4 full waves; a second wave; two workgroups per item; the cap of 64 with the strided loop
+    running twice."""
+    pm = _pm()
+    r = np.random.Generator(np.random.PCG64(26))
+    a, b = _g(r.uniform(0, 1, (2, n, 3)).astype(np.float32)), _g(r.normal(0.5, 0.3, (2, 1000, 3)).astype(np.float32))
+    cd12, cd21, _, _ = pm.chamfer_native(a, b)
+    assert cd12.dtype == torch.float64 and cd21.dtype == torch.float64
+    for cd, (q, t) in ((cd12, (a, b)), (cd21, (b, a))):
+        d2 = pm.nearest_neighbors(q, t)[1].cpu().numpy()
+        assert d2.dtype == np.float64 and d2.shape == q.shape[:2]
+        want = np.array([_fixed_order_mean(d2[k]) for k in range(2)])
+        assert measured(int((cd.cpu().numpy().view(np.int64) != want.view(np.int64)).sum()),
+                        "bit differences between the kernel's mean and the emulated fixed-order sum") <= 0
+
+
 # ------------------------------------------------------------------ degenerate inputs
 
 
