@@ -548,6 +548,21 @@ int nm_gaussian_activate_backward(int32_t k, const float* log_scales, const floa
                                   float scale_modifier, const float* dL_dcov6, const float* dL_dopacity,
                                   float* dL_dlog_scales, float* dL_drot, float* dL_dopacity_logit, void* stream);
 
+/* The raw 3DGS parameters of K deformed Gaussians (what a .ply of a rolled-out frame holds): log_scales (K,3) and rot (K,4) raw,
+ * (r,x,y,z), 16-byte aligned, as nm_gaussian_activate reads them; F (K,3,3) row-major, or NULL for the identity (bitwise the
+ * explicit identity).  log_scales_out (K,3) and rot_out (K,4, unit, r >= 0, 16-byte aligned) satisfy
+ *   nm_gaussian_activate(log_scales_out, rot_out, scale_modifier = 1).cov6
+ *     == strip_symmetric(F L L^T F^T), L = build_rotation(normalize(rot)) diag(scale_modifier exp(log_scales))
+ * so the scale modifier is baked in.  Method: M = F L = U diag(s) V^T by the library's one-sided Jacobi SVD (U in SO(3) also for
+ * det F < 0); the scales are |s_i|, the rotation is U (Shepperd's branch to the quaternion, normalised, sign fixed).  cov' is
+ * never eigen-decomposed: that would square the condition number.
+ * Every output is finite for every finite input whose product F L stays in the fp32 range.  A singular or zero F is legitimate:
+ * each scale is clamped from below at max(1e-20 s_0, 1e-37) before the logarithm (s_0 the largest scale), i.e. at 1e-20 s_0, and
+ * at 1e-37 where s_0 is zero or so small that 1e-20 s_0 lies below it.
+ * The outputs may not overlap the inputs or each other: NM_ERR_INVALID.  No workspace. */
+int nm_gaussian_deform(int32_t k, const float* log_scales, const float* rot, const float* F, float scale_modifier,
+                       float* log_scales_out, float* rot_out, void* stream);
+
 /* SH colour coefficients rotated with the Gaussians (transform_shs_by_rotmat, modules/d3gs/utils/transform_utils.py:41-104):
  * shs_out[g, :, ch] = diag(1, D_1, D_2, D_3)(R) shs_in[g, :, ch], D defined by sum_j c'_j Y_j(R d) = sum_j c_j Y_j(d) for
  * the rasterizer's basis Y, built from R as a polynomial (sh_rotation_matrices of render/transform_utils.py is the same

@@ -139,6 +139,7 @@ SIGNATURES = {
     "nm_regist_backward": (C.c_int, [_I32, _P, _P, _P, _P, _F, _P, _P, _P, _P, _SZ, _P]),
     "nm_gaussian_activate": (C.c_int, [_I32, _P, _P, _P, _F, _P, _P, _P]),
     "nm_gaussian_activate_backward": (C.c_int, [_I32, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P]),
+    "nm_gaussian_deform": (C.c_int, [_I32, _P, _P, _P, _F, _P, _P, _P]),
     "nm_sh_rotate": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P]),
     "nm_sh_rotate_polar": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "nm_sh_rotate_bwd_workspace": (_SZ, [_I32]),

@@ -4,8 +4,8 @@
 
 namespace {
 
-// F.normalize (eps 1e-12); returns the divisor
-__device__ __forceinline__ float qnormalize(const float* v, float* n) {
+// F.normalize (eps 1e-12); returns the divisor.  (This and quat_rot also run on the host: nm_gaussian_deform.h.)
+__host__ __device__ __forceinline__ float qnormalize(const float* v, float* n) {
   const float len = fmaxf(sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]), 1e-12f);
 #pragma unroll
   for (int i = 0; i < 4; ++i) n[i] = v[i] / len;
@@ -13,7 +13,7 @@ __device__ __forceinline__ float qnormalize(const float* v, float* n) {
 }
 
 // build_rotation (general_utils.py:101-124) of an already normalised quaternion
-__device__ __forceinline__ void quat_rot(const float* q, float* M) {
+__host__ __device__ __forceinline__ void quat_rot(const float* q, float* M) {
   const float r = q[0], x = q[1], y = q[2], z = q[3];
   M[0] = 1.f - 2.f * (y * y + z * z); M[1] = 2.f * (x * y - r * z);       M[2] = 2.f * (x * z + r * y);
   M[3] = 2.f * (x * y + r * z);       M[4] = 1.f - 2.f * (x * x + z * z); M[5] = 2.f * (y * z - r * x);

@@ -8,7 +8,12 @@ The YAML's own sim.eps is used here (the reference only overrides it in finetune
 (mediapy) is left to external tools.
 
 `gaussian.rotate_sh: true` (or --rotate_sh; no reference counterpart): from sh_degree 1 the SH colours turn with each
-Gaussian's deformation - rotate_shs_by_deformation once per frame, before the views; the first frame is untouched."""
+Gaussian's deformation - rotate_shs_by_deformation once per frame, before the views; the first frame is untouched.
+
+`--save_gaussians NAME` (no reference counterpart): every frame, the first one included, also goes to
+<result>/<name>/gaussians_NAME/<frame:03d>.ply as a standard 3DGS parameter set (export.save_frame: scaling_modifier baked in, the
+rotated coefficients when rotate_sh is on), also with an empty -dv list; `python -m neuma_amd.replay` renders such a folder from
+any camera."""
 import argparse
 import random
 from pathlib import Path
@@ -18,6 +23,7 @@ import torch
 
 from . import io as nio
 from .config import Cfg, load_config
+from .export import save_frame
 from .finetune import particle_init_data, setup
 from .sim import MPMForwardSim, MPMModelBuilder, MPMStateInitializer, MPMStaticsInitializer
 from .render.transform_utils import rotate_shs_by_deformation
@@ -37,6 +43,8 @@ def parse_args(argv=None):
     p.add_argument("--sim_dt", "-dt", type=float, default=None)
     p.add_argument("--debug_views", "-dv", nargs="+", default=[])
     p.add_argument("--save_particles", "-sp", type=str, default=None)
+    p.add_argument("--save_gaussians", type=str, default=None,
+                   help="Write every frame as a 3DGS .ply into gaussians_<name>/ (replay them with python -m neuma_amd.replay).")
     p.add_argument("--change_base_model", "-cbm", type=str, default=None)
     p.add_argument("--dataset_path", type=str, default=None)
     p.add_argument("--transform_file", type=str, default=None)
@@ -74,6 +82,10 @@ def evaluate(cfg: Cfg, on_frame=None):
     if cfg.get("save_particles") is not None:
         state_root = Path(cfg.get("result_root", RESULT)) / cfg.name / f"states_{cfg.save_particles}"
         state_root.mkdir(parents=True, exist_ok=True)
+    gauss_root = None
+    if cfg.get("save_gaussians") is not None:
+        gauss_root = Path(cfg.get("result_root", RESULT)) / cfg.name / f"gaussians_{cfg.save_gaussians}"
+        gauss_root.mkdir(parents=True, exist_ok=True)
     cfg.video_data.data.init_frame = cfg.get("init_frame")               # NOTE: manually setting (render.py:186-188)
     if cfg.get("debug_views"):
         cfg.video_data.data.used_views = list(cfg.debug_views)
@@ -116,6 +128,8 @@ def evaluate(cfg: Cfg, on_frame=None):
     for vw in views:                                                       # first frame: un-deformed kernels (render.py:292-297)
         render = diff_rasterization(gaussians.get_xyz, None, gaussians, dataset.getCameras(vw, first_step), background, scaling_modifier=scal)
         save_image(render, image_root / f"{vw}_{first_step:03d}.png")
+    if gauss_root is not None:
+        save_frame(gauss_root / f"{first_step:03d}.ply", gaussians, gaussians.get_xyz, scaling_modifier=scal)
     de_x = denormalize_points_helper_func(x, init_data.size, init_data.center)
     de_x_prev, g_prev = de_x.clone().detach(), gaussians.get_xyz.clone().detach()
     for step in range(1, eval_steps + 1):
@@ -129,7 +143,9 @@ def evaluate(cfg: Cfg, on_frame=None):
         means3D = compute_bindings_xyz(de_x, de_x_prev, g_prev, bindings)
         deform_grad = compute_bindings_F(F, bindings)
         images = {}
-        shs = rotate_shs_by_deformation(gaussians.get_features, deform_grad) if rotate_sh and views else None       # once per frame
+        shs = None
+        if rotate_sh and (views or gauss_root is not None):                                                        # once per frame
+            shs = rotate_shs_by_deformation(gaussians.get_features, deform_grad)
         for vw in views:
             cam = dataset.getCameras(vw, first_step)
             if shs is None:
@@ -140,6 +156,8 @@ def evaluate(cfg: Cfg, on_frame=None):
             save_image(images[vw], image_root / f"{vw}_{first_step + step:03d}.png")
         if state_root is not None:
             nio.save_particles_ply(state_root / f"{first_step + step:03d}.ply", x.detach().cpu().numpy())
+        if gauss_root is not None:
+            save_frame(gauss_root / f"{first_step + step:03d}.ply", gaussians, means3D, deform_grad, shs, scal)
         if on_frame is not None:
             on_frame(step, dict(x=x, F=F, means3D=means3D, deform_grad=deform_grad, images=images))
         de_x_prev, g_prev = de_x.clone().detach(), means3D.clone().detach()

@@ -19,6 +19,7 @@ from typing import Callable, Dict, Iterator, List, Optional, Sequence
 import torch
 import torch.nn as nn
 
+from .export import concat_gaussians, deformed_gaussians
 from .material import ComposeMaterial
 from .render.transform_utils import scale_gaussians, translate_gaussians
 from .sim import MPMForwardSim, MPMStateInitializer, MPMStaticsInitializer
@@ -49,10 +50,13 @@ def denormalize_points(points: torch.Tensor, sections: Sequence[int], state_init
 @torch.no_grad()
 def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: int, cameras: Sequence, background: torch.Tensor,
                      denormalize: bool = False, on_frame: Optional[Callable[[int, Dict], None]] = None,
-                     render: bool = True) -> Iterator[Dict]:
+                     render: bool = True, export: bool = False) -> Iterator[Dict]:
     """Generator over frames 0..eval_steps.  Yields {'step', 'x', 'F', 'means3D', 'images': [per camera]}, and with `render`
     'shs', the coefficients the frame was rendered with: those of an object with `rotate_sh` are rotated once per frame, before
-    the views, by the polar rotations of its bound deformation gradients; frame 0 (un-deformed) carries them as loaded."""
+    the views, by the polar rotations of its bound deformation gradients; frame 0 (un-deformed) carries them as loaded.
+    With `export` every frame also carries 'gaussians': one GaussianModel of all objects in object order, the frame as a standard
+    3DGS parameter set (export.deformed_gaussians per object: its own `scaling` baked in, its own `rotate_sh` honoured), and from
+    frame 1 'deform_grad', the bound deformation gradients (K,3,3) it was made from."""
     device = model.device
     state_initializer = MPMStateInitializer(model)
     statics_initializer = MPMStaticsInitializer(model)
@@ -81,6 +85,8 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
         for cam in cameras:
             first["images"].append(diff_rasterization(first["means3D"], None, None, cam, background, sh_deg, cov, opa, shs))
         first["shs"] = shs
+    if export:
+        first["gaussians"] = concat_gaussians([deformed_gaussians(g, g.get_xyz, scaling_modifier=s) for g, s in zip(gs, scal)])
     if on_frame:
         on_frame(0, first)
     yield first
@@ -88,7 +94,7 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
     p_prev = [t.clone().detach() for t in torch.split(de_x, sections, dim=0)]
     k_prev = [g.get_xyz.clone().detach() for g in gs]
     bindings = [o.bindings for o in objects]
-    rotate_sh = [bool(o.rotate_sh) for o in objects] if render and any(o.rotate_sh for o in objects) else None
+    rotate_sh = [bool(o.rotate_sh) for o in objects] if (render or export) and any(o.rotate_sh for o in objects) else None
     for step in range(1, eval_steps + 1):
         stress = elasticity(F)
         state.from_torch(stress=stress)
@@ -108,6 +114,12 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
                 frame["images"].append(diff_rasterization(pack["means3D"], pack["deform_grad"], None, cam, background,
                                                           pack["active_sh_degree"], pack["cov3D"], pack["opacity"], pack["shs"]))
             frame["shs"] = pack["shs"]
+        if export:
+            parts = [torch.split(pack[k], sec_gaussians, dim=0) for k in ("means3D", "deform_grad", "shs")]
+            frame["deform_grad"] = pack["deform_grad"]
+            frame["gaussians"] = concat_gaussians([
+                deformed_gaussians(g, m, dg, sh if (rotate_sh is not None and rotate_sh[i]) else None, s)
+                for i, (g, m, dg, sh, s) in enumerate(zip(gs, *parts, scal))])
         if on_frame:
             on_frame(step, frame)
         yield frame

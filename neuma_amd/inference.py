@@ -12,6 +12,9 @@ for the `experiments/configs/demo/*.yaml` schema (multiobj-bb-cc.yaml, generaliz
     ComposeMaterial over the sections, Gaussians mapped into the simulation box unless `denormalize`        :256-281
     frame 0 from the un-deformed kernels, then per step the loop of infer.simulate_objects                  :283-362
     -> <view>_<step:03d>.png per debug view, <first_step + step:03d>.ply per step when --save_particles
+    -> <result_root>/inference/gaussians_<name>/<step:03d>.ply per frame when --save_gaussians <name> (no reference counterpart): all
+       objects in one standard 3DGS file, each with its own scaling_modifier baked in (infer.simulate_objects(export=True));
+       `python -m neuma_amd.replay` renders the folder from any camera
 
 The numeric work is infer.simulate_objects (the operators of SURVEY 8 f3) on the HIP kernels.  Not reproduced: packing the
 frames into an mp4 (mediapy; --skip_frames / --remove_images are accepted, the latter removes the frames) and the random
@@ -48,6 +51,8 @@ def parse_args(argv=None):
     p.add_argument("--video_name", "-vn", type=str, required=True, help="Save video name.")
     p.add_argument("--debug_views", "-dv", nargs="+", default=[], help="Views for rendering.")
     p.add_argument("--save_particles", "-sp", type=str, default=None, help="Specify the folder name for saving simulated particles.")
+    p.add_argument("--save_gaussians", type=str, default=None,
+                   help="Write every frame as one 3DGS .ply of all objects into inference/gaussians_<name>/ (python -m neuma_amd.replay).")
     p.add_argument("--dataset_path", type=str, default=None, help="Rewrite video dataset path.")
     p.add_argument("--result_root", type=str, default=RESULT)
     p.add_argument("--rotate_sh", action="store_true", help="Rotate every object's SH colours with its deformation (gaussian.rotate_sh).")
@@ -156,6 +161,10 @@ def inference(cfg: Cfg, on_frame=None):
     if cfg.get("save_particles") is not None:
         state_root = root / "inference_states" / f"states_{cfg.save_particles}"
         state_root.mkdir(parents=True, exist_ok=True)
+    gauss_root = None
+    if cfg.get("save_gaussians") is not None:
+        gauss_root = root / "inference" / f"gaussians_{cfg.save_gaussians}"
+        gauss_root.mkdir(parents=True, exist_ok=True)
     eval_steps = int(cfg.eval_steps)
     model = MPMModelBuilder().parse_cfg(cfg.sim).finalize(device, False)          # the YAML's own sim.eps (no override here)
     if cfg.get("dataset_path") is not None:
@@ -171,8 +180,11 @@ def inference(cfg: Cfg, on_frame=None):
     objects = [load_object(o, assets, eval_steps, device, rotate_sh=bool(cfg.get("rotate_sh", False))) for o in cfg.objects]
     views = [vw for vw in dataset.views if vw in debug_views]
     cameras = [dataset.getCameras(vw, first_step) for vw in views]               # the camera of the FIRST step throughout
-    for frame in simulate_objects(model, objects, eval_steps, cameras, background, denormalize=bool(cfg.get("denormalize", False))):
+    for frame in simulate_objects(model, objects, eval_steps, cameras, background, denormalize=bool(cfg.get("denormalize", False)),
+                                  export=gauss_root is not None):
         step = frame["step"]
+        if gauss_root is not None:
+            nio.save_gaussians_ply(frame["gaussians"], gauss_root / f"{step:03d}.ply")
         for vw, img in zip(views, frame["images"]):
             save_image(img, image_root / f"{vw}_{step:03d}.png")
         if state_root is not None and step > 0:
