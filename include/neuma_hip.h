@@ -617,6 +617,33 @@ int nm_state_loss(int32_t n, int32_t kind, float weight_x, float weight_v, const
                   const float* v_gt, const uint8_t* mask, float* loss_out, float* terms_out, float* dL_dx, float* dL_dv,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ Chamfer loss (neuma_amd/pretrain.py, loss: chamfer) */
+
+/* Chamfer loss of the simulated particles x (n,3) against an unordered observation y (m,3), fp32 on the device, fused with its
+ * gradient in x.  No reference counterpart.  mask NULL (all rows) or n bytes: a row with 0 takes no part, neither as a query nor
+ * as a candidate; k = kept rows.  a(i) = the nearest y of kept row i, b(j) = the nearest kept x row of y_j, both by nm_chamfer's
+ * rule (fp64 distances from the fp32 coordinates, lexicographic minimum of (distance^2, index)).
+ *   term_xy = (1/k) sum over kept i of |x_i - y_a(i)|^2,  term_yx = (1/m) sum over j of |y_j - x_b(j)|^2  (both always computed);
+ *   *loss_out (device float) += weight_xy term_xy + weight_yx term_yx: the fp64 value rounded once to fp32, then added;
+ *   terms_out (NULL or 2 device floats) = {term_xy, term_yx}, unweighted, written;
+ *   dL_dx (NULL or (n,3), written) = (2 weight_xy / k)(x_i - y_a(i)) + (2 weight_yx / m) sum over {j: b(j) = i} of (x_i - y_j),
+ *   exactly 0 on dropped rows;  y gets no gradient;
+ *   idx_xy (NULL or n, DEVICE int64) = a(i), -1 on dropped rows;  idx_yx (NULL or m, DEVICE int64) = b(j) in the ORIGINAL row
+ *   numbering of x.
+ * k == 0: the loss gains nothing, terms 0, gradient 0, both index arrays -1.  A NaN / Inf coordinate makes *loss_out NaN and the
+ * affected gradient rows NaN; indices stay in range and the call completes.  n < 1, m < 1, a NULL x / y / loss_out / workspace
+ * or a workspace smaller than nm_chamfer_loss_workspace(n, m) (device scratch, 16-byte aligned; 0 = invalid sizes):
+ * NM_ERR_INVALID before any device work.
+ * Differences and sums in fp64, one fp32 rounding per output; the sum over the observations that chose a row runs in an order
+ * fixed by their indices (stable sort by b, then per-row sums: a thread for a short row, a wave for a long one); no float
+ * atomics: two calls give identical bits, an unaligned view the bits of an aligned copy, and a masked call the bits of the call
+ * on the compacted cloud.  With a mask, k is read back to the host: that call synchronises the stream once (and cannot be
+ * captured into a graph); without a mask there is no synchronisation. */
+size_t nm_chamfer_loss_workspace(int32_t n, int32_t m);
+int nm_chamfer_loss(int32_t n, int32_t m, const float* x, const float* y, const uint8_t* mask, float weight_xy, float weight_yx,
+                    float* loss_out, float* terms_out, float* dL_dx, int64_t* idx_xy, int64_t* idx_yx, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ image-quality metrics (experiments/evaluation.py) */
 
 /* torchmetrics' PeakSignalNoiseRatio and structural_similarity_index_measure (gaussian window 11, sigma 1.5, k1 0.01, k2 0.03,

@@ -169,6 +169,8 @@ SIGNATURES = {
     "nm_classical_bwd": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "nm_state_loss_workspace": (_SZ, [_I32]),
     "nm_state_loss": (C.c_int, [_I32, _I32, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "nm_chamfer_loss_workspace": (_SZ, [_I32, _I32]),
+    "nm_chamfer_loss": (C.c_int, [_I32, _I32, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "nm_lora_merge": (C.c_int, [_I32, _I32, _I32, _F, _P, _P, _P, _P, _P]),
     "nm_lora_merge_bwd": (C.c_int, [_I32, _I32, _I32, _F, _P, _P, _P, _P, _P, _P]),
     "nm_lora_merge_layers": (C.c_int, [_I32, C.POINTER(nm_lora_layer), _P]),

@@ -1,0 +1,221 @@
+// Chamfer loss between the simulated particles x (n,3) and an unordered observation y (m,3), fused with its gradient in x: the
+// loss constitutive pretraining (neuma_amd/pretrain.py, `loss: chamfer`) takes against point clouds that are not in the
+// simulator's particle numbering (chamfer_loss.py).  No reference counterpart.
+//   (rocPRIM select)  with a mask: the kept rows' numbers in ascending order, and their count k.  k is read back to the host
+//                     (the one synchronisation of the masked call; an unmasked call has none): every later step has the size k
+//   k_cl_gather       with a mask: the kept rows as a dense (k,3) cloud - from here on the call IS the call on that cloud, which
+//                     is why both give the same bits
+//   nm_chamfer        (csrc/nm_nn.hip, on a carved sub-workspace) both exact searches, a(i) and b(j), and the two fp64 means
+//                     term_xy, term_yx in its fixed order
+//   k_cl_keys         (b(j), j) pairs for the sort; idx_yx in the caller's row numbering
+//   (rocPRIM radix_sort_pairs, stable)  the pairs by b: every x row owns a contiguous segment with j ascending
+//   k_cl_rows         one thread per kept row: its segment by two binary searches in the sorted keys; a segment of at most
+//                     kClLongRow observations is summed by the thread, j ascending; a longer one by the whole wave, lane l taking
+//                     positions l, l + 64, ... in order and the lanes combined by nm_reduce.h's xor tree - so a row that every
+//                     observation chose (n = 1) is one wave's work.  Writes the gradient row, a(i), and (thread 0) the loss word
+// Differences and sums in fp64, one fp32 rounding per output, no float atomics: the order of every sum depends on the segment
+// alone, two calls give the same bits.  Coordinates are read and gradients written one float at a time: alignment plays no part.
+#include "nm_common.h"
+#include "nm_reduce.h"
+#include "nm_workspace.h"
+
+#include <rocprim/rocprim.hpp>
+
+namespace {
+
+constexpr int kClThreads = 256;
+constexpr int kClLongRow = 32;        // a longer segment goes to the wave
+
+struct ClWs {
+  int* orig;              // n: original number of compacted row i (masked calls)
+  int* kept;              // 1: k
+  void* sel_tmp;
+  size_t sel_bytes;
+  float* xc;              // n * 3: the compacted cloud
+  double* cd;             // 2: term_xy, term_yx
+  int64_t* ia;            // n: a(i), compacted numbering of i
+  int64_t* ib;            // m: b(j), compacted numbering
+  uint32_t *key_in, *key_out, *val_in, *val_out;      // m each
+  void* sort_tmp;
+  size_t sort_bytes;
+  char* chamfer;          // nm_chamfer_workspace(1, n, m)
+  size_t chamfer_bytes;
+};
+
+static ClWs carve_cl(NmCarver& c, int n, int m) {
+  ClWs w;
+  w.orig = c.take<int>(n);
+  w.kept = c.take<int>(1);
+  size_t tb = 0;
+  (void)rocprim::select(nullptr, tb, rocprim::counting_iterator<int>(0), (const uint8_t*)nullptr, (int*)nullptr, (int*)nullptr,
+                        (size_t)n);
+  w.sel_bytes = tb;
+  w.sel_tmp = c.take<char>(tb > 0 ? tb : 1);
+  w.xc = c.take<float>((size_t)n * 3);
+  w.cd = c.take<double>(2);
+  w.ia = c.take<int64_t>(n);
+  w.ib = c.take<int64_t>(m);
+  w.key_in = c.take<uint32_t>(m);
+  w.key_out = c.take<uint32_t>(m);
+  w.val_in = c.take<uint32_t>(m);
+  w.val_out = c.take<uint32_t>(m);
+  tb = 0;
+  (void)rocprim::radix_sort_pairs(nullptr, tb, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
+                                  (size_t)m, 0u, 32u, (hipStream_t)0);
+  w.sort_bytes = tb;
+  w.sort_tmp = c.take<char>(tb > 0 ? tb : 1);
+  w.chamfer_bytes = nm_chamfer_workspace(1, n, m);      // (k <= n rows are searched: the arrays of n rows hold them)
+  w.chamfer = c.take<char>(w.chamfer_bytes);
+  return w;
+}
+
+__global__ void __launch_bounds__(kClThreads) k_cl_gather(int k, const int* __restrict__ orig, const float* __restrict__ x,
+                                                          float* __restrict__ xc) {
+  const int64_t e = (int64_t)blockIdx.x * kClThreads + threadIdx.x;
+  if (e >= 3 * (int64_t)k) return;
+  const int64_t i = e / 3;
+  xc[e] = x[3 * (int64_t)orig[i] + (e - 3 * i)];
+}
+
+__global__ void __launch_bounds__(kClThreads) k_cl_keys(int m, const int64_t* __restrict__ ib, const int* __restrict__ orig,
+                                                        uint32_t* __restrict__ key, uint32_t* __restrict__ val,
+                                                        int64_t* __restrict__ idx_yx) {
+  const int j = blockIdx.x * kClThreads + threadIdx.x;
+  if (j >= m) return;
+  const int64_t b = ib[j];
+  key[j] = (uint32_t)b;
+  val[j] = (uint32_t)j;
+  if (idx_yx) idx_yx[j] = orig ? (int64_t)orig[b] : b;
+}
+
+// first position p in [0, m) with keys[p] >= v, m when there is none
+__device__ __forceinline__ int cl_lower_bound(const uint32_t* __restrict__ keys, int m, uint32_t v) {
+  int lo = 0, hi = m;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (keys[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// x: the (k,3) cloud that was searched; keys / vals: the (b(j), j) pairs sorted by b, j ascending inside a segment
+__global__ void __launch_bounds__(kClThreads) k_cl_rows(int k, int m, float wxy, float wyx, const float* __restrict__ x,
+                                                        const float* __restrict__ y, const int64_t* __restrict__ ia,
+                                                        const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                                                        const int* __restrict__ orig, const double* __restrict__ cd,
+                                                        float* __restrict__ dL_dx, int64_t* __restrict__ idx_xy,
+                                                        float* __restrict__ loss, float* __restrict__ terms) {
+  const int i = blockIdx.x * kClThreads + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const bool live = i < k;              // (no early return: the whole wave takes part in the long rows below)
+  double xi[3] = {0.0, 0.0, 0.0}, sum[3] = {0.0, 0.0, 0.0};
+  int s = 0, e = 0;
+  if (live) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) xi[c] = (double)x[3 * (size_t)i + c];
+    s = cl_lower_bound(keys, m, (uint32_t)i);
+    e = cl_lower_bound(keys, m, (uint32_t)i + 1u);
+  }
+  const bool is_long = e - s > kClLongRow;
+  if (!is_long) {
+    for (int p = s; p < e; ++p) {
+      const size_t j = vals[p];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) sum[c] += xi[c] - (double)y[3 * j + c];
+    }
+  }
+  unsigned long long todo = __ballot(is_long);
+  while (todo) {                        // wave-uniform: one long row of this wave per turn, lowest lane first
+    const int src = __ffsll((long long)todo) - 1;
+    todo &= todo - 1;
+    const int ws = __shfl(s, src, 64), we = __shfl(e, src, 64);
+    double q[3], acc[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) q[c] = __shfl(xi[c], src, 64);
+    for (int p = ws + lane; p < we; p += 64) {
+      const size_t j = vals[p];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) acc[c] += q[c] - (double)y[3 * j + c];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double t = nm_wave_reduce<NmSum>(acc[c]);
+      if (lane == src) sum[c] = t;
+    }
+  }
+  if (live) {
+    const int64_t a = ia[i];
+    const size_t row = orig ? (size_t)orig[i] : (size_t)i;
+    if (dL_dx) {
+      const double cxy = 2.0 * (double)wxy / (double)k, cyx = 2.0 * (double)wyx / (double)m;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) dL_dx[3 * row + c] = (float)(cxy * (xi[c] - (double)y[3 * (size_t)a + c]) + cyx * sum[c]);
+    }
+    if (idx_xy) idx_xy[row] = a;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    *loss = *loss + (float)((double)wxy * cd[0] + (double)wyx * cd[1]);
+    if (terms) {
+      terms[0] = (float)cd[0];
+      terms[1] = (float)cd[1];
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" size_t nm_chamfer_loss_workspace(int32_t n, int32_t m) {
+  if (n < 1 || m < 1 || nm_chamfer_workspace(1, n, m) == 0) return 0;
+  NmCarver c(nullptr);
+  carve_cl(c, n, m);
+  return c.total();
+}
+
+extern "C" int nm_chamfer_loss(int32_t n, int32_t m, const float* x, const float* y, const uint8_t* mask, float weight_xy,
+                               float weight_yx, float* loss_out, float* terms_out, float* dL_dx, int64_t* idx_xy, int64_t* idx_yx,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  NM_REQUIRE(n >= 1 && m >= 1, "empty point cloud");
+  NM_REQUIRE(nm_chamfer_workspace(1, n, m) != 0, "points above 2^31 - 1");
+  NM_REQUIRE(x && y && loss_out && workspace, "null pointer (x, y, loss_out, workspace)");
+  NM_REQUIRE(workspace_bytes >= nm_chamfer_loss_workspace(n, m), "workspace too small (nm_chamfer_loss_workspace)");
+  NM_REQUIRE(((uintptr_t)workspace & 15) == 0, "workspace must be 16-byte aligned");
+  const hipStream_t s = (hipStream_t)stream;
+  NmCarver c(workspace);
+  const ClWs w = carve_cl(c, n, m);
+  int k = n;
+  const float* xs = x;
+  const int* orig = nullptr;
+  if (mask) {
+    size_t tb = w.sel_bytes;
+    NM_HIP_CHECK(rocprim::select(w.sel_tmp, tb, rocprim::counting_iterator<int>(0), mask, w.orig, w.kept, (size_t)n, s));
+    NM_HIP_CHECK(hipMemcpyAsync(&k, w.kept, sizeof(int), hipMemcpyDeviceToHost, s));
+    NM_HIP_CHECK(hipStreamSynchronize(s));
+    NM_REQUIRE(k >= 0 && k <= n, "kept-row count out of range");
+    // rows the mask drops: gradient 0, no neighbour
+    if (dL_dx) NM_HIP_CHECK(hipMemsetAsync(dL_dx, 0, (size_t)n * 3 * sizeof(float), s));
+    if (idx_xy) NM_HIP_CHECK(hipMemsetAsync(idx_xy, 0xFF, (size_t)n * sizeof(int64_t), s));
+    if (k == 0) {
+      if (idx_yx) NM_HIP_CHECK(hipMemsetAsync(idx_yx, 0xFF, (size_t)m * sizeof(int64_t), s));
+      if (terms_out) NM_HIP_CHECK(hipMemsetAsync(terms_out, 0, 2 * sizeof(float), s));
+      return NM_OK;
+    }
+    NM_LAUNCH(k_cl_gather, dim3(nm_div_up(3 * (int64_t)k, kClThreads)), dim3(kClThreads), 0, s, k, (const int*)w.orig, x, w.xc);
+    NM_LAUNCH_CHECK();
+    xs = w.xc;
+    orig = w.orig;
+  }
+  int rc = nm_chamfer(1, k, m, xs, y, w.cd, w.cd + 1, w.ia, w.ib, w.chamfer, w.chamfer_bytes, stream);
+  if (rc != NM_OK) return rc;
+  NM_LAUNCH(k_cl_keys, dim3(nm_div_up(m, kClThreads)), dim3(kClThreads), 0, s, (int)m, (const int64_t*)w.ib, orig, w.key_in, w.val_in,
+            idx_yx);
+  NM_LAUNCH_CHECK();
+  unsigned bits = 1;
+  while (((int64_t)1 << bits) < (int64_t)k) ++bits;
+  size_t tb = w.sort_bytes;
+  NM_HIP_CHECK(rocprim::radix_sort_pairs(w.sort_tmp, tb, w.key_in, w.key_out, w.val_in, w.val_out, (size_t)m, 0u, bits, s));
+  NM_LAUNCH(k_cl_rows, dim3(nm_div_up(k, kClThreads)), dim3(kClThreads), 0, s, k, (int)m, weight_xy, weight_yx, xs, y,
+            (const int64_t*)w.ia, (const uint32_t*)w.key_out, (const uint32_t*)w.val_out, orig, (const double*)w.cd, dL_dx, idx_xy,
+            loss_out, terms_out);
+  NM_LAUNCH_CHECK();
+  return NM_OK;
+}

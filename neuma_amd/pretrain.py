@@ -1,5 +1,5 @@
-"""`python -m neuma_amd.pretrain -c <config.yaml> [--trajectory traj.pt] [--generate_only]` - pretraining of a constitutive pair
-on a particle trajectory: the stage that makes the base model `finetune` and `inference` load through `pretrained_ckpt`.
+"""`python -m neuma_amd.pretrain -c <config.yaml> [--trajectory traj.pt | obs.pt | folder] [--generate_only]` - pretraining of a
+constitutive pair on a particle trajectory or on unordered per-frame point clouds: the stage that makes the base model `finetune` and `inference` load through `pretrained_ckpt`.
 
 The reference has NO counterpart: it ships three NCLaw base models (jelly, plasticine, sand) and not their training.  What is
 here follows NCLaw's recipe on this project's operators - a teacher material (any of the eight classical laws, or a neural
@@ -16,6 +16,10 @@ pair) rolls a body out, the student is fitted to the recorded particle states by
                             (NCLaw's teacher forcing; the gradient chain is cut there).
                             Gradients are zeroed every epoch (the never-zeroed quirk of the reference's LoRA loop belongs to
                             train.finetune_constitutive alone).
+                            `loss: chamfer` replaces the state loss by chamfer_loss(x, traj.x[f]) (nm_chamfer_loss,
+                            chamfer_loss.py): the target of a frame is then an unordered cloud of any size - a CloudTrajectory
+                            (trajectory.py: a file with x0 + clouds, or a folder of NNN.ply observations), or a plain Trajectory
+                            whose x[f] is taken as the cloud.  Velocities are not compared and there is no teacher forcing.
 
 Config (YAML), the reference's schema where it has one:
 
@@ -27,10 +31,10 @@ Config (YAML), the reference's schema where it has one:
     constitution: {elasticity: {...}, plasticity: {...}}              the student; neural or classical by `name` (material.build)
     teacher: {elasticity, plasticity, pretrained_ckpt?}               the teacher; pretrained_ckpt for a neural one.  Not needed
                                                                        with --trajectory
-    pretrain: {...}                                                   PRETRAIN_CFG below
+    pretrain: {...}                                                   PRETRAIN_CFG below (loss: l1 | l2 | chamfer)
     result_root                                                       outputs: <result_root>/pretrain/trajectory.pt, NNNN.pt
 
-Out of scope: a Chamfer (unordered) loss, the native SceneRuntime.epoch path, sharded / multi-GPU pretraining, classical laws
+Out of scope: the native SceneRuntime.epoch path, sharded / multi-GPU pretraining, classical laws
 inside the fused roll-out, several trajectories per epoch, NCLaw's other architectures."""
 import argparse
 import re
@@ -44,16 +48,20 @@ from torch.nn.utils import clip_grad_norm_
 from torch.optim import RAdam
 
 from .material import InvariantFullMetaElasticity, InvariantFullMetaPlasticity, build as build_material
+from .chamfer_loss import chamfer_loss
 from .state_loss import state_loss
 from .train import fetch_scheduler
-from .trajectory import Trajectory, TrajectoryError, model_meta
+from .trajectory import CloudTrajectory, Trajectory, TrajectoryError, load_observations, model_meta
 
 RESULT = "results"
 
 PRETRAIN_CFG = dict(
     num_frames=None,            # None: every recorded frame
     substeps=None,              # None: the trajectory's own
-    num_epochs=300, teacher_steps=0, loss="l2", weight_x=1.0, weight_v=1.0,
+    num_epochs=300, teacher_steps=0,
+    loss="l2",                  # l1 | l2: state_loss on (x, v) in the simulator's numbering (weight_x, weight_v);
+    weight_x=1.0, weight_v=1.0,  # chamfer: chamfer_loss on x against an unordered cloud (weight_xy, weight_yx)
+    weight_xy=1.0, weight_yx=1.0,
     fused="auto",               # auto: fused when both modules are neural | true | false
     reorder="auto",             # particle order of the simulators (MPMFusedDiffSim / MPMCacheDiffSim)
     # The learning rates are NOT tuned on any real material (nor on a synthetic one: the recoveries of tests/test_gpu_pretrain.py
@@ -158,6 +166,29 @@ def epoch_loss(stepper: FrameStepper, traj: Trajectory, num_frames: int, teacher
     return total, terms
 
 
+def chamfer_frame_loss(weight_xy: float = 1.0, weight_yx: float = 1.0, loss=chamfer_loss):
+    """chamfer_loss under epoch_loss's loss_fn signature: x against the frame's cloud x_gt; v, v_gt and the state loss's kind and
+    weights are ignored."""
+    def fn(x, v, x_gt, v_gt, mask, kind=None, weight_x=None, weight_v=None):
+        return loss(x, x_gt, mask, weight_xy=weight_xy, weight_yx=weight_yx)
+    return fn
+
+
+def check_loss_kind(traj, cfg: Dict) -> bool:
+    """Whether the configuration asks for the Chamfer loss; raises, naming the key, where the loss and the observations do not go
+    together.  traj: the observations, or True for point clouds that are not loaded yet."""
+    kind = cfg["loss"]
+    if kind not in ("l1", "l2", "chamfer"):
+        raise ValueError(f"pretrain 'loss' must be l1, l2 or chamfer, not {kind!r}")
+    clouds = traj is True or isinstance(traj, CloudTrajectory)
+    if clouds and kind != "chamfer":
+        raise TrajectoryError(f"point-cloud observations are unordered: 'loss' = {kind!r} compares rows one to one, only "
+                              f"'loss: chamfer' can train on them")
+    if clouds and int(cfg["teacher_steps"]) > 0:
+        raise TrajectoryError(f"'teacher_steps' = {cfg['teacher_steps']}: point-cloud observations hold no state to restart from")
+    return kind == "chamfer"
+
+
 def checkpoints(root: Path) -> List[Path]:
     """NNNN.pt files of a run, oldest first by epoch number"""
     return sorted((p for p in Path(root).glob("*.pt") if re.fullmatch(r"\d{4,}", p.stem)), key=lambda p: int(p.stem))
@@ -179,12 +210,16 @@ def load_checkpoint(path, elasticity, plasticity, device=None) -> dict:
     return ck
 
 
-def pretrain_constitutive(model, statics, traj: Trajectory, elasticity, plasticity, cfg: Optional[Dict] = None, out_root=None,
-                          log=None, loss_fn=state_loss) -> List[float]:
-    """Fit (elasticity, plasticity) to the trajectory; returns the per-epoch losses.  cfg: PRETRAIN_CFG keys.  With `resume` the
-    newest NNNN.pt of out_root is loaded and the epochs are numbered on from it (the schedules start afresh)."""
+def pretrain_constitutive(model, statics, traj, elasticity, plasticity, cfg: Optional[Dict] = None, out_root=None,
+                          log=None, loss_fn=None) -> List[float]:
+    """Fit (elasticity, plasticity) to the trajectory (a Trajectory, or a CloudTrajectory with `loss: chamfer`); returns the
+    per-epoch losses.  cfg: PRETRAIN_CFG keys.  loss_fn: None = state_loss, or the Chamfer adaptor with `loss: chamfer`.  With
+    `resume` the newest NNNN.pt of out_root is loaded and the epochs are numbered on from it (the schedules start afresh)."""
     c = dict(PRETRAIN_CFG)
     c.update(cfg or {})
+    chamfer = check_loss_kind(traj, c)
+    if loss_fn is None:
+        loss_fn = chamfer_frame_loss(float(c["weight_xy"]), float(c["weight_yx"])) if chamfer else state_loss
     device = model.device
     S = int(c["substeps"] if c["substeps"] is not None else traj.meta.get("substeps", 0))
     if S <= 0:
@@ -236,7 +271,7 @@ def pretrain_constitutive(model, statics, traj: Trajectory, elasticity, plastici
             opt.step()
         losses.append(float(loss))
         if log is not None:
-            log(f"[Epoch {epoch}/{last} | L state: {losses[-1]:.4e} | " +
+            log(f"[Epoch {epoch}/{last} | L {'chamfer' if chamfer else 'state'}: {losses[-1]:.4e} | " +
                 " | ".join(f"{tag[0]}-lr: {opt.param_groups[0]['lr']:.2e} | {tag[0]}-gd: {norms[tag]:.2e}" for tag, opt, *_ in opts) + "]")
         if out_root is not None and (step % int(c["ckpt_every"]) == 0 or epoch == last):
             save_checkpoint(out_root / f"{epoch:04d}.pt", elasticity, plasticity, losses[-1])
@@ -254,7 +289,9 @@ def pretrain_constitutive(model, statics, traj: Trajectory, elasticity, plastici
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("--config", "-c", type=str, required=True, help="Path to the config file.")
-    p.add_argument("--trajectory", type=str, default=None, help="Train on this trajectory file instead of generating one.")
+    p.add_argument("--trajectory", type=str, default=None,
+                   help="Train on these observations instead of generating a trajectory: a trajectory file, a point-cloud "
+                        "observation file, or a folder of NNN.ply clouds (loss: chamfer).")
     p.add_argument("--generate_only", action="store_true", help="Write the teacher's trajectory and stop.")
     p.add_argument("--result_root", type=str, default=None)
     return p.parse_args(argv)
@@ -295,20 +332,31 @@ def _init_data(pd, total_steps: int):
 def pretrain(cfg, trajectory=None, generate_only: bool = False, log=print):
     """The entry point's body.  Returns (trajectory path, per-epoch losses)."""
     from .sim import MPMModelBuilder, MPMStateInitializer, MPMStaticsInitializer
+    pc = dict(cfg.get("pretrain") or {})
+    # the observations first: what does not go together raises before any device work
+    folder = trajectory is not None and Path(trajectory).is_dir()
+    if folder:                  # NNN.ply point clouds; their start state is particle_data's (below)
+        check_loss_kind(True, dict(PRETRAIN_CFG, **pc))
+        frames = [int(p.stem) for p in Path(trajectory).glob("*.ply") if p.stem.isdigit()]
+        if not frames or max(frames) < 1:
+            raise TrajectoryError(f"no NNN.ply observation after frame 0 in {trajectory}")
+        T, S = int(pc.get("num_frames") or max(frames)), int(pc.get("substeps") or 0)
+        if S <= 0:
+            raise TrajectoryError("'substeps' per frame must be in the configuration: a folder of clouds has no meta")
+    elif trajectory is not None:
+        traj = load_observations(trajectory)
+        check_loss_kind(traj, dict(PRETRAIN_CFG, **pc))
+        T = int(pc.get("num_frames") or traj.num_frames)
+        S = int(pc.get("substeps") or traj.meta.get("substeps", 0))
+    else:
+        T, S = int(pc["num_frames"]), int(pc["substeps"])
     seed = int(cfg.get("seed", 0))
     np.random.seed(seed); torch.manual_seed(seed)
     device = torch.device(f"cuda:{cfg.get('gpu', 0)}")
     torch.cuda.set_device(device)
     out_root = Path(cfg.get("result_root") or RESULT) / "pretrain"
     out_root.mkdir(parents=True, exist_ok=True)
-    pc = dict(cfg.get("pretrain") or {})
     model = MPMModelBuilder().parse_cfg(cfg.sim).finalize(device, requires_grad=True)
-    if trajectory is not None:
-        traj = Trajectory.load(trajectory)
-        T = int(pc.get("num_frames") or traj.num_frames)
-        S = int(pc.get("substeps") or traj.meta.get("substeps", 0))
-    else:
-        T, S = int(pc["num_frames"]), int(pc["substeps"])
     data = _init_data(cfg.particle_data, T * S)
     state_init, statics_init = MPMStateInitializer(model), MPMStaticsInitializer(model)
     state_init.add_group(data); statics_init.add_group(data)
@@ -322,8 +370,15 @@ def pretrain(cfg, trajectory=None, generate_only: bool = False, log=print):
         log(f"Wrote {traj_path}: {T} frames of {S} substeps, {traj.num_particles} particles")
     else:
         traj_path = Path(trajectory)
+        start = tuple(t.detach().float().cpu() for t in state.to_torch()[:4])
+        if folder:
+            traj = load_observations(trajectory, **dict(zip(("x0", "v0", "C0", "F0"), start)))
         if traj.num_particles != state.particle.x.shape[0]:
             raise TrajectoryError(f"{trajectory} has {traj.num_particles} particles, particle_data gives {state.particle.x.shape[0]}")
+        if isinstance(traj, CloudTrajectory):       # what the observations do not say about the start is particle_data's
+            for key, t in zip(("v0", "C0", "F0"), start[1:]):
+                if getattr(traj, key) is None:
+                    setattr(traj, key, t)
     if generate_only:
         return traj_path, []
     e, p = _build_pair(cfg.constitution, device)
