@@ -166,6 +166,45 @@ int nm_mpm_grid_stats(nm_mpm* h, int32_t* active_blocks, int32_t* nodes_with_mas
 /* Copies the dense grid of the last forward (mv (G,G,G,3), m (G,G,G), v (G,G,G,3)) for tests. */
 int nm_mpm_grid_export(nm_mpm* h, float* mv, float* m, float* v, void* stream);
 
+/* Colliders (no reference counterpart: the reference's only obstacle is the box of mpm.py:373-429).  A collider is a rigid
+ * shape in simulation coordinates (the unit cube; grid node (i,j,k) sits at (i,j,k) dx).  After the box boundary condition
+ * every node with sdf < 0 has its velocity u replaced, collider by collider in list order; with v_c the collider's own
+ * velocity, n its outward unit normal at the node, w = u - v_c and vn = w.n:
+ *   sticky   : u' = v_c
+ *   slip     : u' = u - vn n                                   if vn < 0, else u
+ *   friction : u' = v_c + max(0, 1 + mu vn / |vt|) vt          if vn < 0 (vt = w - vn n; u' = v_c when vt = 0), else u
+ * Shapes: half-space (solid where (p - center).normal < 0), sphere (radial normal; +x at the centre itself), oriented box
+ * (rot: row-major, columns = the box axes in simulation coordinates; the normal at an inside node is the outward axis of the
+ * face with the smallest penetration depth, ties to the lowest axis index).
+ * Geometry is not differentiated; nm_mpm_backward* applies the transposed Jacobians du'/du in reverse list order, with the
+ * colliders the handle holds at the time of the backward call.
+ * Per-operator path only: nm_mpm_forward / _ex and nm_mpm_backward / _ex.  Every other entry point that steps the grid
+ * (nm_mpm_forward_extra, the sharded substep calls, nm_rollout_*) returns NM_ERR_INVALID on a handle that holds colliders. */
+#define NM_MAX_COLLIDERS 8
+#define NM_COLLIDER_PLANE 0
+#define NM_COLLIDER_SPHERE 1
+#define NM_COLLIDER_BOX 2
+#define NM_SURFACE_STICKY 0
+#define NM_SURFACE_SLIP 1
+#define NM_SURFACE_FRICTION 2
+typedef struct nm_collider {
+  int32_t shape;     /* NM_COLLIDER_* */
+  int32_t surface;   /* NM_SURFACE_* */
+  float friction;    /* Coulomb mu >= 0 (friction surface only) */
+  float center[3];   /* plane: a point on it; sphere, box: the centre */
+  float normal[3];   /* plane: unit outward normal */
+  float radius;      /* sphere */
+  float half[3];     /* box: half extents along its own axes */
+  float rot[9];      /* box: rotation, row-major */
+  float velocity[3]; /* v_c */
+} nm_collider;
+/* Host only: validates and copies `n` colliders into the handle (n = 0 removes them); no device work, no synchronisation,
+ * may be called between any two substeps.  NM_ERR_INVALID, with a message that names the field: null handle, n outside
+ * 0..NM_MAX_COLLIDERS, unknown shape / surface, a plane normal that is not unit within 1e-4, a non-positive radius / half
+ * extent, a negative friction, a non-finite centre or velocity, a box rotation that is not orthonormal within 1e-4 or is a
+ * reflection. */
+int nm_mpm_set_colliders(nm_mpm* h, int32_t n, const nm_collider* host);
+
 /* ------------------------------------------------------------------ SVD (modules/nclaw/warp/svd.py) */
 
 /* SVDFunction.forward / batch_svd, svd.py:12-38, 61-96.  F (N,3,3) -> U (N,3,3), sigma (N,3), Vh (N,3,3);

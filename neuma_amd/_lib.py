@@ -37,6 +37,12 @@ class nm_particles(C.Structure):
     _fields_ = [("x", C.c_void_p), ("v", C.c_void_p), ("C", C.c_void_p), ("F", C.c_void_p), ("stress", C.c_void_p)]
 
 
+class nm_collider(C.Structure):
+    _fields_ = [("shape", C.c_int32), ("surface", C.c_int32), ("friction", C.c_float), ("center", C.c_float * 3),
+                ("normal", C.c_float * 3), ("radius", C.c_float), ("half", C.c_float * 3), ("rot", C.c_float * 9),
+                ("velocity", C.c_float * 3)]
+
+
 class nm_mlp(C.Structure):
     _fields_ = [("w0", C.c_void_p), ("w1", C.c_void_p), ("w2", C.c_void_p)]
 
@@ -109,6 +115,7 @@ SIGNATURES = {
     "nm_mpm_backward_finish": (C.c_int, [_P, _I32, C.POINTER(nm_statics), C.POINTER(nm_particles), C.POINTER(nm_particles), _P]),
     "nm_mpm_grid_stats": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_I32), _P]),
     "nm_mpm_grid_export": (C.c_int, [_P, _P, _P, _P, _P]),
+    "nm_mpm_set_colliders": (C.c_int, [_P, _I32, C.POINTER(nm_collider)]),
     "nm_svd3_fwd": (C.c_int, [_I32, _P, _P, _P, _P, _P]),
     "nm_svd3_bwd": (C.c_int, [_I32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nm_material_fwd": (C.c_int, [_I32, _I32, _F, _P, C.POINTER(nm_mlp), _P, _P]),

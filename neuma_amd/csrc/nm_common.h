@@ -32,6 +32,14 @@ void nm_set_error(const char* fmt, ...);
       return NM_ERR_INVALID;                                                                    \
     }                                                                                           \
   } while (0)
+// NM_REQUIRE with a printf-style message (the format must be a string literal)
+#define NM_REQUIREF(cond, fmt, ...)                                                                   \
+  do {                                                                                                \
+    if (!(cond)) {                                                                                    \
+      nm_set_error("invalid argument: " fmt " (%s:%d)", __VA_ARGS__, __FILE__, __LINE__);            \
+      return NM_ERR_INVALID;                                                                          \
+    }                                                                                                 \
+  } while (0)
 
 // kernel timing hooks (nm_api.hip)
 void nm_prof_begin(const char* name, hipStream_t s);
@@ -61,6 +69,9 @@ int nm_mpm_shared_counters(nm_mpm* h, int** cnt, int** pos);
 int nm_mpm_xchg_arrays(nm_mpm* h, int** slot, int** dil, int* new_tag);   // frame-level exchange: slot[] (-1 between frames), dil[]
 int nm_mpm_grid_dims(const nm_mpm* h);                                    // blocks per axis
 int nm_mpm_dil_tag(const nm_mpm* h);
+int nm_mpm_num_colliders(const nm_mpm* h);                                // nm_mpm_set_colliders; the kernels are in nm_mpm.hip
+// entry points outside the per-operator substep refuse a handle that holds colliders
+#define NM_REFUSE_COLLIDERS(h) NM_REQUIRE(nm_mpm_num_colliders(h) == 0, "colliders: per-operator path only")
 int nm_shard_slots(nm_mpm* h, const int32_t* shared, int32_t cap_shared, int assign, void* stream);
 int nm_shard_pack_fwd(nm_mpm* h, const int32_t* shared, int32_t cap_shared, float* buf, unsigned char* mine, int32_t* status,
                       void* stream);

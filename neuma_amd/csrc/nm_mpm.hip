@@ -18,6 +18,7 @@
 //     padding blocks whose velocity is defined as zero.
 #include "nm_common.h"
 #include "nm_grid.h"
+#include "nm_collide.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -50,7 +51,9 @@ struct nm_mpm {
   int resident_epoch;         // ... as long as the epoch has not moved: the reverse sweep's first substep then restores nothing
   int gv_stale;   // the last clear left the velocity array alone (GridPrologue keep_gv): the next grid update zeroes what dropped out
   int fresh_rows; // g2p writes a fresh state's values into the rows of disabled particles (roll-out checkpoints, nm_grid.h)
+  ColliderSet colliders;   // nm_mpm_set_colliders (host copy; travels by value in the arguments of the collider kernels)
 };
+int nm_mpm_num_colliders(const nm_mpm* h) { return h->colliders.n; }
 void nm_mpm_set_fresh_rows(nm_mpm* h, int on) { h->fresh_rows = on; }
 
 #ifdef NM_PHASES
@@ -1048,6 +1051,61 @@ __global__ void __launch_bounds__(256) k_grid_op_bwd(const int* __restrict__ lis
   }
 }
 
+// Colliders (nm_collide.h) on the active blocks, behind the grid update: one wave per 4x4x4 block, one lane per node, like
+// k_grid_op.  Rewrites the velocities of the nodes inside a collider in place; every other node is left as it is.
+__global__ void __launch_bounds__(256) k_grid_collide(const int* __restrict__ list, const int* __restrict__ count,
+                                                      float4* __restrict__ gv, MpmK K, ColliderSet S) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int cnt = *count;
+  for (int li = blockIdx.x * 4 + wave; li < cnt; li += gridDim.x * 4) {
+    const int b = list[li];
+    int i, j, k;
+    block_coords(b, K.nb, lane, i, j, k);
+    if (!(i < K.G && j < K.G && k < K.G)) continue;      // padding nodes: velocity defined as zero
+    const int node = (b << 6) + lane;
+    const float p[3] = {(float)i * K.dx, (float)j * K.dx, (float)k * K.dx};
+    float4 q = gv[node];
+    float u[3] = {q.x, q.y, q.z};
+    bool hit = false;
+    for (int c = 0; c < S.n; ++c) hit = collide_apply(S.c[c], p, u) || hit;
+    if (hit) gv[node] = make_float4(u[0], u[1], u[2], q.w);
+  }
+}
+
+// adjoint of k_grid_collide, in front of k_grid_op_bwd: gg {dL/du'} -> {dL/du}, u the velocity behind the box boundary
+// condition.  u is recomputed from {mv, m} through grid_velocity and the transposed Jacobians are applied in reverse order.
+// The velocity collider c saw is replayed from u for every c that holds the node (at most 28 collide_apply for a node inside all
+// 8 colliders) instead of kept: a history indexed by the collider went to scratch memory (212 bytes per lane).
+__global__ void __launch_bounds__(256) k_grid_collide_bwd(const int* __restrict__ list, const int* __restrict__ count,
+                                                          const float4* __restrict__ gm, float4* __restrict__ gg, MpmK K,
+                                                          ColliderSet S) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int cnt = *count;
+  for (int li = blockIdx.x * 4 + wave; li < cnt; li += gridDim.x * 4) {
+    const int b = list[li];
+    int i, j, k;
+    block_coords(b, K.nb, lane, i, j, k);
+    if (!(i < K.G && j < K.G && k < K.G)) continue;
+    const int node = (b << 6) + lane;
+    const float p[3] = {(float)i * K.dx, (float)j * K.dx, (float)k * K.dx};
+    float u0[3], mk[3], n_[3];
+    grid_velocity(K, i, j, k, gm[node], u0, mk);
+    u0[0] *= mk[0]; u0[1] *= mk[1]; u0[2] *= mk[2];
+    bool hit = false;
+    for (int c = 0; c < S.n; ++c) hit = collide_normal(S.c[c], p, n_) || hit;
+    if (!hit) continue;
+    float4 q = gg[node];
+    float g[3] = {q.x, q.y, q.z};
+    for (int c = S.n - 1; c >= 0; --c) {
+      if (!collide_normal(S.c[c], p, n_)) continue;      // outside this one: identity, nothing to replay
+      float u[3] = {u0[0], u0[1], u0[2]};
+      for (int e = 0; e < c; ++e) collide_apply(S.c[e], p, u);
+      collide_adjoint(S.c[c], p, u, g);
+    }
+    gg[node] = make_float4(g[0], g[1], g[2], q.w);
+  }
+}
+
 // mpm.py:432-498 (body: g2p_particle, nm_grid.h)
 __global__ void __launch_bounds__(256, 3) k_g2p(MpmK K, int n, const float* __restrict__ clip, const int* __restrict__ enabled,
                                              const float* x, const float* v, const float* C, const float* F,
@@ -1298,7 +1356,7 @@ __global__ void k_grid_stats(const float4* __restrict__ gm, const int* __restric
 // dense (G,G,G) view of the block-sparse grid, as the reference's arrays read after grid_op: blocks the last substep did
 // not touch hold m = mv = 0 and v = BC(g dt) (the dense sweep of mpm.py:373-429 visits every node)
 __global__ void k_grid_export(MpmK K, const float4* __restrict__ gm, const float4* __restrict__ gv, float* mv, float* m,
-                              float* v, const int* __restrict__ flags, int epoch) {
+                              float* v, const int* __restrict__ flags, int epoch, ColliderSet S) {
   int t = blockIdx.x * blockDim.x + threadIdx.x;
   int G = K.G;
   if (t >= G * G * G) return;
@@ -1309,7 +1367,10 @@ __global__ void k_grid_export(MpmK K, const float4* __restrict__ gm, const float
     q = make_float4(0.f, 0.f, 0.f, 0.f);
     float w[3], mk[3];
     grid_velocity(K, i, j, k, q, w, mk);
-    u = make_float4(w[0] * mk[0], w[1] * mk[1], w[2] * mk[2], 0.f);
+    w[0] *= mk[0]; w[1] *= mk[1]; w[2] *= mk[2];
+    const float p[3] = {(float)i * K.dx, (float)j * K.dx, (float)k * K.dx};
+    for (int c = 0; c < S.n; ++c) collide_apply(S.c[c], p, w);      // (the dense sweep would have visited this node too)
+    u = make_float4(w[0], w[1], w[2], 0.f);
   }
   if (mv) { mv[3 * t] = q.x; mv[3 * t + 1] = q.y; mv[3 * t + 2] = q.z; }
   if (m) m[t] = q.w;
@@ -1366,6 +1427,7 @@ extern "C" int nm_mpm_create(const nm_mpm_cfg* cfg, nm_mpm** out) {
   h->gv_stale = 0;
   h->resident_rec = nullptr; h->resident_epoch = -1;
   h->sh_cnt = h->sh_pos = nullptr;
+  h->colliders.n = 0;
   *out = h;
   return NM_OK;
 }
@@ -1455,6 +1517,23 @@ static int launch_grid_op(nm_mpm* h, void* save, int cap, const int* skip, int32
   NM_LAUNCH_CHECK();
   return NM_OK;
 }
+// colliders behind the grid update (or behind a restore): not launched when the handle holds none
+static int launch_grid_collide(nm_mpm* h, hipStream_t s) {
+  if (h->colliders.n == 0) return NM_OK;
+  const int now = h->cur;
+  NM_LAUNCH(k_grid_collide, dim3(kSweepGrid), dim3(256), 0, s, (const int*)h->list[now], (const int*)(h->count + now), h->gv, h->k,
+                     h->colliders);
+  NM_LAUNCH_CHECK();
+  return NM_OK;
+}
+static int launch_grid_collide_bwd(nm_mpm* h, hipStream_t s) {
+  if (h->colliders.n == 0) return NM_OK;
+  const int now = h->cur;
+  NM_LAUNCH(k_grid_collide_bwd, dim3(kSweepGrid), dim3(256), 0, s, (const int*)h->list[now], (const int*)(h->count + now),
+                     (const float4*)h->gm, h->gg, h->k, h->colliders);
+  NM_LAUNCH_CHECK();
+  return NM_OK;
+}
 static int launch_g2p(nm_mpm* h, int n, const nm_statics* st, const nm_particles* cur, nm_particles* next, hipStream_t s) {
   NM_LAUNCH(k_g2p, dim3(nm_div_up(n, 256)), dim3(256), 0, s, h->k, n, st->clip_bound, st->enabled, cur->x, cur->v, cur->C,
                      cur->F, h->gv, next->x, next->v, next->C, next->F, h->fresh_rows);
@@ -1498,11 +1577,13 @@ static int mpm_build_grid(nm_mpm* h, int n, const nm_statics* st, const nm_parti
     NM_LAUNCH(k_grid_restore, dim3(kSweepGrid), dim3(256), 0, s, h->k, rrec, h->gm, h->gv, h->list[h->cur], h->count + h->cur);
     NM_LAUNCH_CHECK();
     skip = rrec.hdr;
-    if (restore_verified) return NM_OK;   // the host has seen this record's header: it is valid, nothing to fall back to
+    if (restore_verified) return launch_grid_collide(h, s);   // the host has seen this record's header: it is valid, nothing to fall back to
   }
   if (n > 0) rc = launch_p2g(h, n, st, cur, skip, s);
   if (rc) return rc;
-  return launch_grid_op(h, save, cap, skip, nullptr, nullptr, take_dropped(h), s);
+  rc = launch_grid_op(h, save, cap, skip, nullptr, nullptr, take_dropped(h), s);
+  if (rc) return rc;
+  return launch_grid_collide(h, s);      // (a valid restored record made the grid update return at once: still one pass)
 }
 
 // ---- roll-out only: the clear / restore of a substep rides in the prologue of the constitutive kernel in front of it
@@ -1608,6 +1689,7 @@ int nm_mpm_g2p_fuse(nm_mpm* h, const nm_statics* st, const nm_particles* cur, nm
 extern "C" int nm_mpm_forward_extra(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur, int32_t n_extra,
                                     const nm_statics* st_extra, nm_particles* extra, void* stream) {
   NM_REQUIRE(h, "null handle");
+  NM_REFUSE_COLLIDERS(h);
   NM_REQUIRE(n >= 0 && n_extra >= 0, "negative particle count");
   int rc = NM_OK;
   if (n > 0) rc = check_particles(st, cur, true);
@@ -1664,7 +1746,9 @@ int nm_mpm_backward_cached_begin(nm_mpm* h, int32_t n, const nm_statics* st, con
 int nm_mpm_backward_cached_finish(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur, nm_particles* gcur,
                                   const void* stamp_rec, int32_t cap_blocks, const float* xbuf, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  int rc = launch_grid_op_bwd(h, stamp_rec, cap_blocks, h->epoch + 1, xbuf, s);
+  int rc = launch_grid_collide_bwd(h, s);
+  if (rc) return rc;
+  rc = launch_grid_op_bwd(h, stamp_rec, cap_blocks, h->epoch + 1, xbuf, s);
   if (rc || n == 0) return rc;
   return launch_p2g_bwd(h, n, st, cur, gcur, s);
 }
@@ -1743,6 +1827,7 @@ int nm_mpm_shared_counters(nm_mpm* h, int** cnt, int** pos) {
 
 extern "C" int nm_mpm_p2g(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur, void* stream) {
   NM_REQUIRE(h, "null handle");
+  NM_REFUSE_COLLIDERS(h);
   NM_REQUIRE(n >= 0, "negative particle count");
   if (n > 0) {
     int rc = check_particles(st, cur, true);
@@ -1757,6 +1842,7 @@ extern "C" int nm_mpm_p2g(nm_mpm* h, int32_t n, const nm_statics* st, const nm_p
 extern "C" int nm_mpm_forward_finish(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur, nm_particles* next,
                                      void* gridrec, int32_t cap_blocks, int32_t* status, void* stream) {
   NM_REQUIRE(h, "null handle");
+  NM_REFUSE_COLLIDERS(h);
   NM_REQUIRE(!gridrec || cap_blocks > 0, "grid cache record without capacity");
   NM_REQUIRE(n >= 0, "negative particle count");
   hipStream_t s = (hipStream_t)stream;
@@ -1773,6 +1859,7 @@ extern "C" int nm_mpm_backward_begin(nm_mpm* h, int32_t n, const nm_statics* st,
                                      const nm_particles* gnext, nm_particles* gcur, const void* gridrec, int32_t cap_blocks,
                                      void* stream) {
   NM_REQUIRE(h, "null handle");
+  NM_REFUSE_COLLIDERS(h);
   NM_REQUIRE(gridrec && cap_blocks > 0, "the sharded reverse sweep needs the substep's grid cache record");
   NM_REQUIRE(n >= 0, "negative particle count");
   hipStream_t s = (hipStream_t)stream;
@@ -1788,14 +1875,59 @@ extern "C" int nm_mpm_backward_begin(nm_mpm* h, int32_t n, const nm_statics* st,
 extern "C" int nm_mpm_backward_finish(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur, nm_particles* gcur,
                                       void* stream) {
   NM_REQUIRE(h, "null handle");
+  NM_REFUSE_COLLIDERS(h);
   NM_REQUIRE(n >= 0, "negative particle count");
   hipStream_t s = (hipStream_t)stream;
+  // (no launch_grid_collide_bwd here: NM_REFUSE_COLLIDERS above is what keeps colliders off the sharded substep; lifting it means
+  //  adding that launch in front of this one, as in nm_mpm_backward_cached_finish)
   int rc = launch_grid_op_bwd(h, nullptr, 0, 0, nullptr, s);
   if (rc || n == 0) return rc;
   rc = check_particles(st, cur, true);
   if (!rc) rc = check_grad_out(gcur);
   if (rc) return rc;
   return launch_p2g_bwd(h, n, st, cur, gcur, s);
+}
+
+// ---- colliders: host-side validation and copy into the handle (no device work)
+static bool finite1(float v) { return fabsf(v) <= 3.402823466e+38f; }      // (NaN fails the comparison)
+static bool finite3(const float* v) { return finite1(v[0]) && finite1(v[1]) && finite1(v[2]); }
+extern "C" int nm_mpm_set_colliders(nm_mpm* h, int32_t n, const nm_collider* host) {
+  NM_REQUIRE(h, "colliders: null handle");
+  NM_REQUIREF(n >= 0 && n <= NM_MAX_COLLIDERS, "colliders: n = %d outside 0..%d", n, NM_MAX_COLLIDERS);
+  NM_REQUIRE(n == 0 || host, "colliders: null array");
+  for (int q = 0; q < n; ++q) {
+    const nm_collider& c = host[q];
+    NM_REQUIREF(c.shape == NM_COLLIDER_PLANE || c.shape == NM_COLLIDER_SPHERE || c.shape == NM_COLLIDER_BOX,
+                "collider %d: shape: unknown shape %d", q, c.shape);
+    NM_REQUIREF(c.surface == NM_SURFACE_STICKY || c.surface == NM_SURFACE_SLIP || c.surface == NM_SURFACE_FRICTION,
+                "collider %d: surface: unknown surface %d", q, c.surface);
+    NM_REQUIREF(c.friction >= 0.f && finite1(c.friction), "collider %d: friction: must not be negative", q);
+    NM_REQUIREF(finite3(c.center), "collider %d: center: three finite numbers expected", q);
+    NM_REQUIREF(finite3(c.velocity), "collider %d: velocity: three finite numbers expected", q);
+    if (c.shape == NM_COLLIDER_PLANE) {
+      const double l2 = (double)c.normal[0] * c.normal[0] + (double)c.normal[1] * c.normal[1] + (double)c.normal[2] * c.normal[2];
+      NM_REQUIREF(fabs(sqrt(l2) - 1.0) <= 1e-4, "collider %d: normal: not a unit vector", q);
+    } else if (c.shape == NM_COLLIDER_SPHERE) {
+      NM_REQUIREF(c.radius > 0.f && finite1(c.radius), "collider %d: radius: must be positive", q);
+    } else {
+      NM_REQUIREF(c.half[0] > 0.f && c.half[1] > 0.f && c.half[2] > 0.f && finite3(c.half), "collider %d: half: extents must be positive", q);
+      bool ortho = true;
+      for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) {
+          double d = 0.0;
+          for (int r = 0; r < 3; ++r) d += (double)c.rot[3 * r + a] * c.rot[3 * r + b];
+          if (!(fabs(d - (a == b ? 1.0 : 0.0)) <= 1e-4)) ortho = false;
+        }
+      NM_REQUIREF(ortho, "collider %d: rot: not orthonormal", q);
+      const float* r = c.rot;
+      const double det = (double)r[0] * ((double)r[4] * r[8] - (double)r[5] * r[7]) - (double)r[1] * ((double)r[3] * r[8] - (double)r[5] * r[6]) +
+                         (double)r[2] * ((double)r[3] * r[7] - (double)r[4] * r[6]);
+      NM_REQUIREF(det > 0.0, "collider %d: rot: not orthonormal (a reflection: determinant -1)", q);
+    }
+  }
+  h->colliders.n = n;
+  for (int q = 0; q < n; ++q) h->colliders.c[q] = host[q];
+  return NM_OK;
 }
 
 extern "C" int nm_mpm_grid_stats(nm_mpm* h, int32_t* active_blocks, int32_t* nodes_with_mass, void* stream) {
@@ -1817,7 +1949,7 @@ extern "C" int nm_mpm_grid_export(nm_mpm* h, float* mv, float* m, float* v, void
   NM_REQUIRE(h, "null handle");
   int G = h->k.G;
   NM_LAUNCH(k_grid_export, dim3(nm_div_up((int64_t)G * G * G, 256)), dim3(256), 0, (hipStream_t)stream, h->k,
-                     h->gm, h->gv, mv, m, v, h->flags, h->epoch);
+                     h->gm, h->gv, mv, m, v, h->flags, h->epoch, h->colliders);
   NM_LAUNCH_CHECK();
   return NM_OK;
 }

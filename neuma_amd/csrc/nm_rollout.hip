@@ -482,6 +482,7 @@ extern "C" int nm_rollout_forward(nm_mpm* h, int32_t n, const nm_rollout_cfg* cf
                                   void* stream) {
   NM_REQUIRE(h && cfg && st && we && wp && states, "null pointer");
   NM_REQUIRE(n >= 0 && cfg->substeps >= 1, "bad sizes");
+  NM_REFUSE_COLLIDERS(h);
   return rollout_forward_sweep(h, n, cfg, st, we, wp, states, gridcache, workspace, workspace_bytes, nullptr, stream);
 }
 
@@ -491,6 +492,7 @@ extern "C" int nm_rollout_backward(nm_mpm* h, int32_t n, const nm_rollout_cfg* c
                                    void* stream) {
   NM_REQUIRE(h && cfg && st && we && wp && states && gstate_last && gstate_first && gw_e && gw_p, "null pointer");
   NM_REQUIRE(n >= 0 && cfg->substeps >= 1, "bad sizes");
+  NM_REFUSE_COLLIDERS(h);
   return rollout_backward_sweep(h, n, cfg, st, we, wp, states, gridcache, gstate_last, gstate_first, gw_e, gw_p, workspace,
                                 workspace_bytes, nullptr, stream);
 }
@@ -503,6 +505,7 @@ extern "C" int nm_rollout_forward_sharded(nm_mpm* h, int32_t n, const nm_rollout
                                           void* stream) {
   NM_REQUIRE(h && cfg && st && we && wp && (states || n == 0), "null pointer");
   NM_REQUIRE(n >= 0 && cfg->substeps >= 1, "bad sizes");
+  NM_REFUSE_COLLIDERS(h);
   ShardCtx c;
   int rc = shard_args_ok(comm, cap, cap_shared, cfg, gridcache, shard_ws, shard_ws_bytes, c);
   if (rc) return rc;
@@ -516,6 +519,7 @@ extern "C" int nm_rollout_backward_sharded(nm_mpm* h, int32_t n, const nm_rollou
                                            size_t shard_ws_bytes, void* stream) {
   NM_REQUIRE(h && cfg && st && we && wp && gw_e && gw_p && ((states && gstate_last && gstate_first) || n == 0), "null pointer");
   NM_REQUIRE(n >= 0 && cfg->substeps >= 1, "bad sizes");
+  NM_REFUSE_COLLIDERS(h);
   ShardCtx c;
   int rc = shard_args_ok(comm, cap, cap_shared, cfg, gridcache, shard_ws, shard_ws_bytes, c);
   if (rc) return rc;

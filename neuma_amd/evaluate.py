@@ -26,6 +26,7 @@ from .config import Cfg, load_config
 from .export import save_frame
 from .finetune import particle_init_data, setup
 from .sim import MPMForwardSim, MPMModelBuilder, MPMStateInitializer, MPMStaticsInitializer
+from .sim.colliders import describe as describe_colliders
 from .render.transform_utils import rotate_shs_by_deformation
 from .tune import compute_bindings_F, compute_bindings_xyz, denormalize_points_helper_func, diff_rasterization
 
@@ -112,6 +113,8 @@ def evaluate(cfg: Cfg, on_frame=None):
     if cfg.get("sim_dt") is not None:
         cfg.sim.dt = cfg.sim_dt
     model = MPMModelBuilder().parse_cfg(cfg.sim).finalize(device, False)
+    if model.colliders:
+        print(describe_colliders(model.colliders))
     sim = MPMForwardSim(model)
     state_initializer, statics_initializer = MPMStateInitializer(model), MPMStaticsInitializer(model)
     init_data = particle_init_data(cfg, eval_steps)
@@ -136,6 +139,7 @@ def evaluate(cfg: Cfg, on_frame=None):
         stress = E(F)
         state.from_torch(stress=stress)
         x, v, C, F = sim(statics, state)
+        model.step_colliders()                                               # moving colliders: one substep further (sim/colliders.py)
         F = P(F)
         state.from_torch(F=F)
         statics_initializer.update(statics, step)

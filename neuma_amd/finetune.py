@@ -27,6 +27,7 @@ from .harness import DiskRuntime
 from .material import InvariantFullMetaElasticity, InvariantFullMetaPlasticity
 from .prepare import prepare_simulation_data
 from .sim import MPMInitData
+from .sim.colliders import refuse_in_training as refuse_colliders_in_training
 from .train import finetune_constitutive, optimize_init_velocity
 
 EPS = 6e-7          # finetune.py:47
@@ -94,6 +95,7 @@ def _views(dataset, spec):
 
 
 def finetune(cfg: Cfg, log=print):
+    refuse_colliders_in_training(cfg, "python -m neuma_amd.finetune")
     if bool(cfg.gaussian.get("rotate_sh", False)):
         raise NotImplementedError("`gaussian.rotate_sh: true` rotates the SH colours with the deformation in the forward renderers only "
                                   "(python -m neuma_amd.render / neuma_amd.inference): training would need the colours' gradient with "

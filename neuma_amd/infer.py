@@ -99,6 +99,7 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
         stress = elasticity(F)
         state.from_torch(stress=stress)
         x, v, C, F = sim(statics, state)
+        model.step_colliders()                                         # moving colliders: one substep further (sim/colliders.py)
         F = plasticity(F)
         state.from_torch(F=F)
         statics_initializer.update(statics, step)

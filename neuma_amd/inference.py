@@ -38,6 +38,7 @@ from .infer import SceneObject, simulate_objects
 from .material import InvariantFullMetaElasticity, InvariantFullMetaPlasticity, build as build_material
 from .prepare import prepare_simulation_data
 from .sim import MPMInitData, MPMModelBuilder
+from .sim.colliders import describe as describe_colliders
 
 RESULT = "results"
 
@@ -167,6 +168,8 @@ def inference(cfg: Cfg, on_frame=None):
         gauss_root.mkdir(parents=True, exist_ok=True)
     eval_steps = int(cfg.eval_steps)
     model = MPMModelBuilder().parse_cfg(cfg.sim).finalize(device, False)          # the YAML's own sim.eps (no override here)
+    if model.colliders:
+        print(describe_colliders(model.colliders))
     if cfg.get("dataset_path") is not None:
         cfg.video_data.data.path = cfg.dataset_path
         print(f"Rewrite video dataset path to\n\t{cfg.dataset_path}")

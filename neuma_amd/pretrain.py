@@ -332,6 +332,8 @@ def _init_data(pd, total_steps: int):
 def pretrain(cfg, trajectory=None, generate_only: bool = False, log=print):
     """The entry point's body.  Returns (trajectory path, per-epoch losses)."""
     from .sim import MPMModelBuilder, MPMStateInitializer, MPMStaticsInitializer
+    from .sim.colliders import refuse_in_training
+    refuse_in_training(cfg, "python -m neuma_amd.pretrain")
     pc = dict(cfg.get("pretrain") or {})
     # the observations first: what does not go together raises before any device work
     folder = trajectory is not None and Path(trajectory).is_dir()

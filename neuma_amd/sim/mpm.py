@@ -17,6 +17,7 @@ from torch import Tensor
 
 from .abstract import State, Model, ModelBuilder, StateInitializer, StaticsInitializer
 from .. import _lib as L
+from . import colliders as _colliders
 
 
 def _cfg_get(cfg, key, default=None):
@@ -205,12 +206,15 @@ class MPMModel(Model):
         self.grid_cache = "auto"
         self._cache_blocks = None
         self.exchange = None        # set by shard(): this model steps one rank's share of the particles
+        self._colliders = []        # set_colliders(): rigid obstacles of the per-operator path (sim/colliders.py)
 
     def shard(self, group=None, cap=None, cap_shared=None, cap_dil=None, cap_frame=None):
         """Make this model one rank of a particle-sharded simulation (sim/shard.py): every forward / backward sums the
         grid blocks it shares with other ranks over `group`.  Capacities default to 1.5x what the first substep needs
         (cap, cap_shared: per-substep lists and grid cache records; cap_dil, cap_frame: the fused roll-out's frame-level
         neighbourhood and exchange lists)."""
+        if self._colliders:
+            raise L.NeumaHipError("colliders: per-operator path only (a model with colliders cannot be sharded)")
         from .shard import GridExchange
         self.exchange = GridExchange(self, group, cap, cap_shared, cap_dil, cap_frame)
         return self.exchange
@@ -246,7 +250,36 @@ class MPMModel(Model):
             with torch.cuda.device(self.device):
                 L.check(L.lib().nm_mpm_create(C.byref(cfg), C.byref(out)), "nm_mpm_create")
             self._handle = out
+            self._upload_colliders()
         return self._handle
+
+    # -- colliders (no reference counterpart; sim/colliders.py)
+    @property
+    def colliders(self):
+        """The colliders this model steps against (Plane / Sphere / Box objects, in the order they are applied)."""
+        return list(self._colliders)
+
+    def set_colliders(self, colliders) -> None:
+        """Replace the model's colliders (dicts as in the `sim.colliders` config list, or collider objects; [] / None removes
+        them).  Host-only: may be called between any two substeps.  Colliders act on MPMModel.forward / backward (the per-operator
+        path); the fused roll-out, forward_extra and sharded models refuse them."""
+        if self.exchange is not None:
+            raise L.NeumaHipError("colliders: per-operator path only (set_colliders on a sharded model)")
+        self._colliders = _colliders.parse_colliders(colliders)
+        if self._handle is not None:      # (a handle created later takes them along: handle())
+            self._upload_colliders()
+
+    def _upload_colliders(self) -> None:
+        arr = _colliders.pack(self._colliders)
+        L.check(L.lib().nm_mpm_set_colliders(self._handle, len(self._colliders), arr), "nm_mpm_set_colliders")
+
+    def step_colliders(self) -> None:
+        """Advance the centres of the moving colliders by velocity * dt (one substep) and re-upload; nothing when none moves."""
+        if not any(c.moving for c in self._colliders):
+            return
+        dt = float(self.constant.dt)
+        self._colliders = [c.advanced(dt) if c.moving else c for c in self._colliders]
+        self._upload_colliders()
 
     def __del__(self):
         try:
@@ -337,6 +370,7 @@ class MPMModelBuilder(ModelBuilder):
     def __init__(self) -> None:
         super().__init__()
         self.reserve("bc")
+        self.colliders = []      # optional `colliders` list of the sim node (not a reserved key: a config without it is ready)
 
     def parse_cfg(self, cfg) -> 'MPMModelBuilder':
         num_grids = int(_cfg_req(cfg, "num_grids"))
@@ -348,6 +382,7 @@ class MPMModelBuilder(ModelBuilder):
         self.config['inv_dx'] = float(num_grids)
         self.config['bc'] = str(_cfg_req(cfg, "bc"))
         self.config['eps'] = float(_cfg_req(cfg, "eps"))
+        self.colliders = _colliders.parse_colliders(_cfg_get(cfg, "colliders"))
         return self
 
     def build_constant(self) -> MPMConstant:
@@ -362,7 +397,10 @@ class MPMModelBuilder(ModelBuilder):
         bc = self.config['bc']
         if bc not in ('freeslip', 'noslip'):
             raise ValueError('invalid boundary condition: {}'.format(bc))   # mpm.py:550
-        return MPMModel(self.build_constant(), device, requires_grad, bc=bc)
+        model = MPMModel(self.build_constant(), device, requires_grad, bc=bc)
+        if self.colliders:
+            model.set_colliders(self.colliders)
+        return model
 
 
 def _per_particle(values, counts, dtype, device) -> Tensor:
