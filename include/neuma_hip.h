@@ -205,6 +205,56 @@ typedef struct nm_collider {
  * reflection. */
 int nm_mpm_set_colliders(nm_mpm* h, int32_t n, const nm_collider* host);
 
+/* Drawing colliders (no reference counterpart; kernels: csrc/nm_draw.hip + csrc/nm_collide_ray.h; the same definition in fp64:
+ * neuma_amd/extras/collider_draw.py; prose: DESIGN.md section 7).  Three calls in front of and behind unchanged
+ * nm_raster_forward_ex renders; nothing here is differentiated.
+ * Coordinates: colliders live in simulation coordinates, renders in render coordinates, p_r = a * p_s + b per axis (map_a,
+ *   map_b: 3 host floats each, a > 0).  Rays are cast in simulation space from o_s = (o_r - b) / a with the UN-normalised
+ *   direction d_s = d_r / a (d_r a unit vector), so the ray parameter t is the render-space distance for any a > 0; a
+ *   render-space normal is normalize(n_s / a).
+ * Drawn solid of a collider: its shape cut by the unit cube [0,1]^3 (the only region where it acts on the grid; a half-space
+ *   gets a finite body).  Both are convex: the ray is inside for t in (t_in, t_out), t_in the largest entry and t_out the
+ *   smallest exit over the constraints - the half-space's inequality / the sphere's quadratic / the box's three slabs in its
+ *   own frame, then the cube's three slabs.  The normal at t_in is that of the constraint that gave it (of equal entries the
+ *   first in the order shape, cube x, y, z).  Hit: t_in < t_out and t_out > 0, at t = max(t_in, 0); t_in < 0 means the
+ *   origin is inside: t = 0 and the normal faces the camera.
+ * Pixel ray: origin cfg->campos; direction through the point that cfg's projmatrix maps to the pixel's centre, ndc
+ *   ((2 px + 1) / W - 1, (2 py + 1) / H - 1), on the far plane (ndc z = 1): with inv_proj = projmatrix^-1 (16 host doubles,
+ *   row-major, row-vector convention hom = clip inv_proj; the caller inverts in fp64) the direction is
+ *   hom.xyz - hom.w campos for clip = (x, y, 1, 1), folded in fp64 on the host.  The nearest hit over the colliders wins
+ *   (of equal t the first in list order).
+ * Shade: rgb = color * k * (0.35 + 0.65 max(0, n_r.l)), l = -d_r (the unit vector from the hit to the camera: a headlight).
+ *   k = 0.8 on the odd cells, floor(cu) + floor(cv) odd, of a checkerboard on a plane's own face when its style has
+ *   checker > 0: (cu, cv) = ((p_s - center).u, (p_s - center).v) / checker with the frame e = the coordinate axis along which
+ *   |normal| is smallest (the lowest of equal ones), u = normalize(normal x e), v = normal x u; k = 1 everywhere else (cube
+ *   faces, spheres, boxes, camera inside).
+ * Occlusion is per Gaussian, not per pixel: a Gaussian is hidden when the segment o_s + u (mean_s - o_s), u in (0, 1), meets a
+ *   drawn solid before u = 1 or the mean lies inside one: u_in < u_out, u_out > 0 and u_in < 1.  It is shown or dropped as a
+ *   whole by its centre.
+ * Frame: besides img_all (the usual render over the configured background) the caller renders, with opacity_front and bg = 0,
+ *   rgb_front (the frame's colours) and a_front (channel 0 of a colors_precomp = 1 render); then out = rgb_front +
+ *   (1 - a_front) shade where hit >= 0 and out = img_all, bit for bit, elsewhere. */
+struct nm_raster_cfg; /* the rasterizer's per-view settings, below */
+typedef struct nm_collider_style {
+  float color[3]; /* rgb in 0..1 */
+  float checker;  /* planes: checkerboard cell size in simulation units, 0 = plain; ignored for spheres and boxes */
+} nm_collider_style;
+/* t (H,W; +inf where nothing is hit), shade (3,H,W; 0 there), hit (H,W int32: collider index or -1) for the whole image of
+ * cfg (image_height, image_width, campos are read).  n = 0 is valid.  NM_ERR_INVALID, naming the field: null pointers, n outside
+ * 0..NM_MAX_COLLIDERS, a <= 0 (map_a), non-finite style values / map / camera / inv_proj, and nm_mpm_set_colliders' geometry
+ * checks (shape, center, normal, radius, half, rot). */
+int nm_collider_cast(const struct nm_raster_cfg* cfg, const double* inv_proj, const float* map_a, const float* map_b, int32_t n,
+                     const nm_collider* colliders, const nm_collider_style* styles, float* t, float* shade, int32_t* hit,
+                     void* stream);
+/* opacity_front (K,1) = 0 where the Gaussian at means3D (K,3; render coordinates) is hidden from campos (3 host floats, render
+ * coordinates), opacity (K,1) elsewhere; hidden (K uint8, may be NULL) = the flags.  Same validation. */
+int nm_collider_hide(const float* campos, const float* map_a, const float* map_b, int32_t n, const nm_collider* colliders,
+                     int32_t k, const float* means3D, const float* opacity, float* opacity_front, uint8_t* hidden, void* stream);
+/* out (3,H,W) from img_all, rgb_front, shade (3,H,W), a_front (H,W: channel 0 of the alpha render) and hit (H,W).  Writes the
+ * pixel rows of cfg's stripe [16 tile_y0, 16 tile_y1) only (every row when tile_y1 <= tile_y0). */
+int nm_collider_compose(const struct nm_raster_cfg* cfg, const float* img_all, const float* rgb_front, const float* a_front,
+                        const float* shade, const int32_t* hit, float* out, void* stream);
+
 /* ------------------------------------------------------------------ SVD (modules/nclaw/warp/svd.py) */
 
 /* SVDFunction.forward / batch_svd, svd.py:12-38, 61-96.  F (N,3,3) -> U (N,3,3), sigma (N,3), Vh (N,3,3);

@@ -43,6 +43,10 @@ class nm_collider(C.Structure):
                 ("velocity", C.c_float * 3)]
 
 
+class nm_collider_style(C.Structure):
+    _fields_ = [("color", C.c_float * 3), ("checker", C.c_float)]
+
+
 class nm_mlp(C.Structure):
     _fields_ = [("w0", C.c_void_p), ("w1", C.c_void_p), ("w2", C.c_void_p)]
 
@@ -116,6 +120,11 @@ SIGNATURES = {
     "nm_mpm_grid_stats": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_I32), _P]),
     "nm_mpm_grid_export": (C.c_int, [_P, _P, _P, _P, _P]),
     "nm_mpm_set_colliders": (C.c_int, [_P, _I32, C.POINTER(nm_collider)]),
+    "nm_collider_cast": (C.c_int, [C.POINTER(nm_raster_cfg), C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_float), _I32,
+                                  C.POINTER(nm_collider), C.POINTER(nm_collider_style), _P, _P, _P, _P]),
+    "nm_collider_hide": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), _I32, C.POINTER(nm_collider), _I32,
+                                  _P, _P, _P, _P, _P]),
+    "nm_collider_compose": (C.c_int, [C.POINTER(nm_raster_cfg), _P, _P, _P, _P, _P, _P, _P]),
     "nm_svd3_fwd": (C.c_int, [_I32, _P, _P, _P, _P, _P]),
     "nm_svd3_bwd": (C.c_int, [_I32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nm_material_fwd": (C.c_int, [_I32, _I32, _F, _P, C.POINTER(nm_mlp), _P, _P]),

@@ -13,7 +13,10 @@ Gaussian's deformation - rotate_shs_by_deformation once per frame, before the vi
 `--save_gaussians NAME` (no reference counterpart): every frame, the first one included, also goes to
 <result>/<name>/gaussians_NAME/<frame:03d>.ply as a standard 3DGS parameter set (export.save_frame: scaling_modifier baked in, the
 rotated coefficients when rotate_sh is on), also with an empty -dv list; `python -m neuma_amd.replay` renders such a folder from
-any camera."""
+any camera.
+
+`--draw_colliders` (or `sim.draw_colliders: true`; no reference counterpart): the colliders of `sim.colliders` are drawn into every
+frame, under the inverse of the ori_bounds -> sim_bounds alignment (neuma_amd/collider_draw.py)."""
 import argparse
 import random
 from pathlib import Path
@@ -21,7 +24,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import io as nio
+from . import collider_draw, io as nio
 from .config import Cfg, load_config
 from .export import save_frame
 from .finetune import particle_init_data, setup
@@ -52,6 +55,7 @@ def parse_args(argv=None):
     p.add_argument("--alpha", type=float, default=None)
     p.add_argument("--result_root", type=str, default=RESULT)
     p.add_argument("--rotate_sh", action="store_true", help="Rotate the SH colours with the deformation (gaussian.rotate_sh).")
+    p.add_argument("--draw_colliders", action="store_true", help="Draw the colliders of sim.colliders into every frame (sim.draw_colliders).")
     return p.parse_args(argv)
 
 
@@ -113,8 +117,14 @@ def evaluate(cfg: Cfg, on_frame=None):
     if cfg.get("sim_dt") is not None:
         cfg.sim.dt = cfg.sim_dt
     model = MPMModelBuilder().parse_cfg(cfg.sim).finalize(device, False)
+    draw_styles = None
+    if collider_draw.wanted(cfg, cfg.sim):
+        if model.colliders:
+            draw_styles = collider_draw.parse_styles(cfg.sim.get("colliders"))
+        else:
+            print("draw_colliders: sim.colliders is empty, nothing to draw")
     if model.colliders:
-        print(describe_colliders(model.colliders))
+        print(describe_colliders(model.colliders, drawn=draw_styles is not None))
     sim = MPMForwardSim(model)
     state_initializer, statics_initializer = MPMStateInitializer(model), MPMStaticsInitializer(model)
     init_data = particle_init_data(cfg, eval_steps)
@@ -128,9 +138,21 @@ def evaluate(cfg: Cfg, on_frame=None):
     views = [vw for vw in dataset.views if vw in cfg.get("debug_views", [])]
     scal = cfg.gaussian.get("scaling_modifier", 1.0)
     rotate_sh = bool(cfg.get("rotate_sh", False) or cfg.gaussian.get("rotate_sh", False)) and gaussians.active_sh_degree > 0
+    to_render = collider_draw.map_from_alignment(init_data.size, init_data.center)      # renders are de-normalised (below)
+
+    def drawn(img, cam, means3D, deform_grad, shs):
+        """the view with the colliders drawn in, at the centres the model holds now (collider_draw.draw)"""
+        if draw_styles is None:
+            return img
+        cov, opa = gaussians.get_covariance(scaling_modifier=scal), gaussians.get_opacity
+        front = collider_draw.front_renderer(means3D, deform_grad, cam, gaussians.active_sh_degree, cov,
+                                             gaussians.get_features if shs is None else shs)
+        return collider_draw.draw(img, cam, model.colliders, draw_styles, to_render, front, means3D, opa)
+
     for vw in views:                                                       # first frame: un-deformed kernels (render.py:292-297)
-        render = diff_rasterization(gaussians.get_xyz, None, gaussians, dataset.getCameras(vw, first_step), background, scaling_modifier=scal)
-        save_image(render, image_root / f"{vw}_{first_step:03d}.png")
+        cam = dataset.getCameras(vw, first_step)
+        render = diff_rasterization(gaussians.get_xyz, None, gaussians, cam, background, scaling_modifier=scal)
+        save_image(drawn(render, cam, gaussians.get_xyz, None, None), image_root / f"{vw}_{first_step:03d}.png")
     if gauss_root is not None:
         save_frame(gauss_root / f"{first_step:03d}.ply", gaussians, gaussians.get_xyz, scaling_modifier=scal)
     de_x = denormalize_points_helper_func(x, init_data.size, init_data.center)
@@ -157,6 +179,7 @@ def evaluate(cfg: Cfg, on_frame=None):
             else:
                 images[vw] = diff_rasterization(means3D, deform_grad, None, cam, background, gaussians.active_sh_degree,
                                                 gaussians.get_covariance(scaling_modifier=scal), gaussians.get_opacity, shs)
+            images[vw] = drawn(images[vw], cam, means3D, deform_grad, shs)
             save_image(images[vw], image_root / f"{vw}_{first_step + step:03d}.png")
         if state_root is not None:
             nio.save_particles_ply(state_root / f"{first_step + step:03d}.ply", x.detach().cpu().numpy())

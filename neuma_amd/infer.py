@@ -19,6 +19,7 @@ from typing import Callable, Dict, Iterator, List, Optional, Sequence
 import torch
 import torch.nn as nn
 
+from . import collider_draw
 from .export import concat_gaussians, deformed_gaussians
 from .material import ComposeMaterial
 from .render.transform_utils import scale_gaussians, translate_gaussians
@@ -50,13 +51,15 @@ def denormalize_points(points: torch.Tensor, sections: Sequence[int], state_init
 @torch.no_grad()
 def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: int, cameras: Sequence, background: torch.Tensor,
                      denormalize: bool = False, on_frame: Optional[Callable[[int, Dict], None]] = None,
-                     render: bool = True, export: bool = False) -> Iterator[Dict]:
+                     render: bool = True, export: bool = False, draw_styles=None) -> Iterator[Dict]:
     """Generator over frames 0..eval_steps.  Yields {'step', 'x', 'F', 'means3D', 'images': [per camera]}, and with `render`
     'shs', the coefficients the frame was rendered with: those of an object with `rotate_sh` are rotated once per frame, before
     the views, by the polar rotations of its bound deformation gradients; frame 0 (un-deformed) carries them as loaded.
     With `export` every frame also carries 'gaussians': one GaussianModel of all objects in object order, the frame as a standard
     3DGS parameter set (export.deformed_gaussians per object: its own `scaling` baked in, its own `rotate_sh` honoured), and from
-    frame 1 'deform_grad', the bound deformation gradients (K,3,3) it was made from."""
+    frame 1 'deform_grad', the bound deformation gradients (K,3,3) it was made from.
+    With `draw_styles` (collider_draw.parse_styles of the model's colliders) every image has the colliders drawn in, at the centres
+    the model holds for that frame; `denormalize` then needs one alignment for all objects (ValueError otherwise)."""
     device = model.device
     state_initializer = MPMStateInitializer(model)
     statics_initializer = MPMStaticsInitializer(model)
@@ -77,13 +80,28 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
             scale_gaussians(g, float(gd.size[0]), torch.zeros(3, device=device))
             translate_gaussians(g, torch.as_tensor(gd.center, dtype=torch.float32, device=device))
     sh_deg = gs[0].active_sh_degree
+    to_render = collider_draw.IDENTITY
+    if draw_styles is not None and denormalize:
+        maps = [collider_draw.map_from_alignment(gd.size, gd.center) for gd in state_initializer.groups]
+        if any(m != maps[0] for m in maps[1:]):
+            raise ValueError("draw_colliders with denormalize: the objects' ori_bounds -> sim_bounds alignments differ, so there is no "
+                             "single render space to draw the colliders in (render without denormalize, or align the objects alike)")
+        to_render = maps[0]
+
+    def drawn(img, cam, means3D, deform_grad, cov, opa, shs):
+        if draw_styles is None:
+            return img
+        return collider_draw.draw(img, cam, model.colliders, draw_styles, to_render,
+                                  collider_draw.front_renderer(means3D, deform_grad, cam, sh_deg, cov, shs), means3D, opa)
+
     first = dict(step=0, x=x.clone(), F=F.clone(), means3D=torch.cat([g.get_xyz for g in gs], 0), images=[])
     if render:
         cov = torch.cat([g.get_covariance(s) for g, s in zip(gs, scal)], 0)
         opa = torch.cat([g.get_opacity for g in gs], 0)
         shs = torch.cat([g.get_features for g in gs], 0)
         for cam in cameras:
-            first["images"].append(diff_rasterization(first["means3D"], None, None, cam, background, sh_deg, cov, opa, shs))
+            img = diff_rasterization(first["means3D"], None, None, cam, background, sh_deg, cov, opa, shs)
+            first["images"].append(drawn(img, cam, first["means3D"], None, cov, opa, shs))
         first["shs"] = shs
     if export:
         first["gaussians"] = concat_gaussians([deformed_gaussians(g, g.get_xyz, scaling_modifier=s) for g, s in zip(gs, scal)])
@@ -112,8 +130,9 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
         frame = dict(step=step, x=x.clone(), F=F.clone(), means3D=pack["means3D"], images=[])
         if render:
             for cam in cameras:
-                frame["images"].append(diff_rasterization(pack["means3D"], pack["deform_grad"], None, cam, background,
-                                                          pack["active_sh_degree"], pack["cov3D"], pack["opacity"], pack["shs"]))
+                img = diff_rasterization(pack["means3D"], pack["deform_grad"], None, cam, background,
+                                         pack["active_sh_degree"], pack["cov3D"], pack["opacity"], pack["shs"])
+                frame["images"].append(drawn(img, cam, pack["means3D"], pack["deform_grad"], pack["cov3D"], pack["opacity"], pack["shs"]))
             frame["shs"] = pack["shs"]
         if export:
             parts = [torch.split(pack[k], sec_gaussians, dim=0) for k in ("means3D", "deform_grad", "shs")]

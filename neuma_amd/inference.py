@@ -16,6 +16,9 @@ for the `experiments/configs/demo/*.yaml` schema (multiobj-bb-cc.yaml, generaliz
        objects in one standard 3DGS file, each with its own scaling_modifier baked in (infer.simulate_objects(export=True));
        `python -m neuma_amd.replay` renders the folder from any camera
 
+    -> with --draw_colliders (or `sim.draw_colliders: true`; no reference counterpart) the colliders of `sim.colliders` are drawn into
+       every frame (neuma_amd/collider_draw.py); with `denormalize` the objects must then share one ori_bounds -> sim_bounds alignment
+
 The numeric work is infer.simulate_objects (the operators of SURVEY 8 f3) on the HIP kernels.  Not reproduced: packing the
 frames into an mp4 (mediapy; --skip_frames / --remove_images are accepted, the latter removes the frames) and the random
 initial velocity of an object without `particle_data.vel` - the reference's own fallback `sample_vel(seed=42)` raises (it
@@ -30,7 +33,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import io as nio
+from . import collider_draw, io as nio
 from .config import Cfg, load_config
 from .dataset import CameraDataset
 from .evaluate import save_image
@@ -57,6 +60,7 @@ def parse_args(argv=None):
     p.add_argument("--dataset_path", type=str, default=None, help="Rewrite video dataset path.")
     p.add_argument("--result_root", type=str, default=RESULT)
     p.add_argument("--rotate_sh", action="store_true", help="Rotate every object's SH colours with its deformation (gaussian.rotate_sh).")
+    p.add_argument("--draw_colliders", action="store_true", help="Draw the colliders of sim.colliders into every frame (sim.draw_colliders).")
     return p.parse_args(argv)
 
 
@@ -168,8 +172,14 @@ def inference(cfg: Cfg, on_frame=None):
         gauss_root.mkdir(parents=True, exist_ok=True)
     eval_steps = int(cfg.eval_steps)
     model = MPMModelBuilder().parse_cfg(cfg.sim).finalize(device, False)          # the YAML's own sim.eps (no override here)
+    draw_styles = None
+    if collider_draw.wanted(cfg, cfg.sim):
+        if model.colliders:
+            draw_styles = collider_draw.parse_styles(cfg.sim.get("colliders"))
+        else:
+            print("draw_colliders: sim.colliders is empty, nothing to draw")
     if model.colliders:
-        print(describe_colliders(model.colliders))
+        print(describe_colliders(model.colliders, drawn=draw_styles is not None))
     if cfg.get("dataset_path") is not None:
         cfg.video_data.data.path = cfg.dataset_path
         print(f"Rewrite video dataset path to\n\t{cfg.dataset_path}")
@@ -184,7 +194,7 @@ def inference(cfg: Cfg, on_frame=None):
     views = [vw for vw in dataset.views if vw in debug_views]
     cameras = [dataset.getCameras(vw, first_step) for vw in views]               # the camera of the FIRST step throughout
     for frame in simulate_objects(model, objects, eval_steps, cameras, background, denormalize=bool(cfg.get("denormalize", False)),
-                                  export=gauss_root is not None):
+                                  export=gauss_root is not None, draw_styles=draw_styles):
         step = frame["step"]
         if gauss_root is not None:
             nio.save_gaussians_ply(frame["gaussians"], gauss_root / f"{step:03d}.ply")

@@ -187,11 +187,11 @@ def pack(colliders: Sequence):
     return arr
 
 
-def describe(colliders: Sequence) -> str:
-    """One line per collider, for the entry points' start-up print."""
+def describe(colliders: Sequence, drawn: bool = False) -> str:
+    """One line per collider, for the entry points' start-up print.  drawn: the run draws them (neuma_amd/collider_draw.py)."""
     if not colliders:
         return "colliders: none"
-    lines = [f"colliders: {len(colliders)} (not drawn in renders)"]
+    lines = [f"colliders: {len(colliders)} ({'drawn' if drawn else 'not drawn'} in renders)"]
     for i, c in enumerate(colliders):
         if isinstance(c, Plane):
             geo = f"plane point={c.point} normal={tuple(round(a, 6) for a in c.normal)}"
