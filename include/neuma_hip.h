@@ -205,6 +205,39 @@ typedef struct nm_collider {
  * reflection. */
 int nm_mpm_set_colliders(nm_mpm* h, int32_t n, const nm_collider* host);
 
+/* Field colliders (no reference counterpart; device functions: csrc/nm_collide_field.h; the same definition in fp64 torch:
+ * neuma_amd/extras/colliders.py apply_field_collider): a rigid obstacle whose shape is a signed distance field phi (negative
+ * inside) sampled on a regular lattice - node (ix, iy, iz) at origin + (ix, iy, iz) spacing in simulation coordinates, value
+ * phi[(ix ny + iy) nz + iz] - e.g. the field of a closed triangle mesh (neuma_amd/mesh_sdf.py).  At the grid node at p:
+ *   q = (p - origin) / spacing; the node is outside unless 0 <= q_a <= dims_a - 1 on all three axes (a NaN is outside);
+ *   cell i_a = min(floor(q_a), dims_a - 2), fraction t = q - i;
+ *   phi(p) = the trilinear interpolant of the cell's eight corner values: along z a_xy = f_xy0 + t_z (f_xy1 - f_xy0), along y
+ *   b_x = a_x0 + t_y (a_x1 - a_x0), along x phi = b_0 + t_x (b_1 - b_0);
+ *   the node is inside iff phi(p) < 0;
+ *   the normal is n = g / |g|, g the analytic gradient of that same interpolant in t: g_x = b_1 - b_0, g_y = the x-interpolant
+ *   of a_x1 - a_x0, g_z = the xy-interpolant of f_xy1 - f_xy0; n = +x where |g| = 0 (as the sphere at its centre).
+ * Given n, the collider's own velocity v_c, its surface and mu, the response is exactly the sticky / slip / friction law of
+ * the colliders above, and nm_mpm_backward* applies its transposed Jacobian du'/du; geometry is not differentiated.  Field
+ * colliders are applied behind ALL analytic colliders, in list order, and their adjoints in reverse in front of the analytic
+ * ones.  With none set no kernel is launched for them.  `origin` is the position of lattice node (0,0,0) NOW: a moving
+ * collider is moved by the caller (origin += velocity dt, set again).  Every entry point that refuses a handle holding
+ * colliders (above) refuses one holding field colliders, with the same message. */
+#define NM_MAX_FIELD_COLLIDERS 4
+typedef struct nm_field_collider {
+  int32_t surface;   /* NM_SURFACE_* */
+  float friction;    /* Coulomb mu >= 0 (friction surface only) */
+  float velocity[3]; /* v_c */
+  float origin[3];   /* simulation coordinates of lattice node (0,0,0), now */
+  float spacing;     /* lattice spacing > 0 */
+  int32_t dims[3];   /* nodes per axis, each >= 2, at most 2^27 in all */
+  const float* phi;  /* DEVICE, prod(dims) floats; the caller keeps it alive while the handle holds the collider */
+} nm_field_collider;
+/* Host only, like nm_mpm_set_colliders: validates and copies `n` field colliders into the handle (n = 0 removes them); no device
+ * work, no synchronisation.  NM_ERR_INVALID, with a message that names the field: null handle, n outside
+ * 0..NM_MAX_FIELD_COLLIDERS, unknown surface, a negative friction, a non-finite origin or velocity, spacing <= 0, a dim < 2, more
+ * than 2^27 nodes, a null phi.  A refused call leaves the set as it was. */
+int nm_mpm_set_field_colliders(nm_mpm* h, int32_t n, const nm_field_collider* host);
+
 /* Drawing colliders (no reference counterpart; kernels: csrc/nm_draw.hip + csrc/nm_collide_ray.h; the same definition in fp64:
  * neuma_amd/extras/collider_draw.py; prose: DESIGN.md section 7).  Three calls in front of and behind unchanged
  * nm_raster_forward_ex renders; nothing here is differentiated.
@@ -802,6 +835,24 @@ int nm_chamfer(int32_t b, int32_t n1, int32_t n2, const float* p1, const float* 
 size_t nm_mesh_inside_workspace(int32_t n_tris, int32_t n_points);
 int nm_points_in_mesh(int32_t n_verts, int32_t n_tris, int32_t n_points, const double* verts, const int32_t* tris,
                       const double* points, uint8_t* inside_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ mesh distance field (no reference counterpart) */
+
+/* Unsigned distance of the nodes of a regular lattice to a triangle mesh (kernels: csrc/nm_sdf.hip; the same definition in
+ * numpy, fp64 and fp32: neuma_amd/extras/mesh_sdf.py, whose module docstring spells the per-triangle formula - closest point
+ * by Voronoi region - operation by operation).  verts (n_verts, 3) fp32 and tris (n_tris, 3) int32 contiguous on the DEVICE;
+ * origin (3 floats) and dims (3 ints) on the HOST.  dist_out[(ix ny + iy) nz + iz] (DEVICE, fp32) = the minimum over the kept
+ * triangles of the distance from origin + (ix, iy, iz) spacing to the triangle, evaluated in fp32 without fma contraction and
+ * with correctly rounded division and square root; +inf when no triangle is kept.  A triangle with a vertex index outside
+ * [0, n_verts) is dropped and never read; a triangle whose squared area aa cc - bb^2 is not above 1e-6 aa cc (aa, bb, cc the
+ * dot products of its two edges at the first vertex) counts as the union of its three edge segments, a zero-length segment
+ * as a point.  Vertices are expected to be finite.  The minimum does not depend on the order of the triangles; no float
+ * atomics, no host synchronisation: two calls give identical bytes.  workspace: nm_mesh_distance_workspace(n_tris, n_nodes)
+ * bytes of device scratch (0 = invalid sizes).  -1 before any device work: negative sizes, n_tris > 2^24, a dim < 2, more
+ * than 2^27 nodes, a spacing that is not positive and finite, a non-finite origin, a too small workspace. */
+size_t nm_mesh_distance_workspace(int32_t n_tris, int64_t n_nodes);
+int nm_mesh_distance(int32_t n_verts, int32_t n_tris, const float* verts, const int32_t* tris, const float* origin, float spacing,
+                     const int32_t* dims, float* dist_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ Gaussian fill (particles out of the density field) */
 

@@ -43,6 +43,11 @@ class nm_collider(C.Structure):
                 ("velocity", C.c_float * 3)]
 
 
+class nm_field_collider(C.Structure):
+    _fields_ = [("surface", C.c_int32), ("friction", C.c_float), ("velocity", C.c_float * 3), ("origin", C.c_float * 3),
+                ("spacing", C.c_float), ("dims", C.c_int32 * 3), ("phi", C.c_void_p)]
+
+
 class nm_collider_style(C.Structure):
     _fields_ = [("color", C.c_float * 3), ("checker", C.c_float)]
 
@@ -120,6 +125,7 @@ SIGNATURES = {
     "nm_mpm_grid_stats": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_I32), _P]),
     "nm_mpm_grid_export": (C.c_int, [_P, _P, _P, _P, _P]),
     "nm_mpm_set_colliders": (C.c_int, [_P, _I32, C.POINTER(nm_collider)]),
+    "nm_mpm_set_field_colliders": (C.c_int, [_P, _I32, C.POINTER(nm_field_collider)]),
     "nm_collider_cast": (C.c_int, [C.POINTER(nm_raster_cfg), C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_float), _I32,
                                   C.POINTER(nm_collider), C.POINTER(nm_collider_style), _P, _P, _P, _P]),
     "nm_collider_hide": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), _I32, C.POINTER(nm_collider), _I32,
@@ -174,6 +180,8 @@ SIGNATURES = {
     "nm_chamfer": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "nm_mesh_inside_workspace": (_SZ, [_I32, _I32]),
     "nm_points_in_mesh": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
+    "nm_mesh_distance_workspace": (_SZ, [_I32, _I64]),
+    "nm_mesh_distance": (C.c_int, [_I32, _I32, _P, _P, C.POINTER(C.c_float), _F, C.POINTER(_I32), _P, _P, _SZ, _P]),
     "nm_fill_gaussians": (C.c_int, [_I32, _P, _P, _P, C.POINTER(C.c_double), C.c_double, C.POINTER(_I32), _F, _P, _P, _P, _P, _P]),
     "nm_fill_density_workspace": (_SZ, [_I32, _I64, _I32]),
     "nm_fill_density": (C.c_int, [_I32, _I64, _P, _P, _P, C.POINTER(C.c_double), C.c_double, C.POINTER(_I32), _F, _P, _P, _SZ, _P]),

@@ -19,6 +19,7 @@
 #include "nm_common.h"
 #include "nm_grid.h"
 #include "nm_collide.h"
+#include "nm_collide_field.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -52,8 +53,9 @@ struct nm_mpm {
   int gv_stale;   // the last clear left the velocity array alone (GridPrologue keep_gv): the next grid update zeroes what dropped out
   int fresh_rows; // g2p writes a fresh state's values into the rows of disabled particles (roll-out checkpoints, nm_grid.h)
   ColliderSet colliders;   // nm_mpm_set_colliders (host copy; travels by value in the arguments of the collider kernels)
+  FieldColliderSet fields; // nm_mpm_set_field_colliders (likewise; the phi arrays stay the caller's)
 };
-int nm_mpm_num_colliders(const nm_mpm* h) { return h->colliders.n; }
+int nm_mpm_num_colliders(const nm_mpm* h) { return h->colliders.n + h->fields.n; }      // analytic and field colliders alike
 void nm_mpm_set_fresh_rows(nm_mpm* h, int on) { h->fresh_rows = on; }
 
 #ifdef NM_PHASES
@@ -1106,6 +1108,61 @@ __global__ void __launch_bounds__(256) k_grid_collide_bwd(const int* __restrict_
   }
 }
 
+// Field colliders (nm_collide_field.h) on the active blocks, behind k_grid_collide: the same sweep, in list order.
+__global__ void __launch_bounds__(256) k_grid_collide_field(const int* __restrict__ list, const int* __restrict__ count,
+                                                            float4* __restrict__ gv, MpmK K, FieldColliderSet S) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int cnt = *count;
+  for (int li = blockIdx.x * 4 + wave; li < cnt; li += gridDim.x * 4) {
+    const int b = list[li];
+    int i, j, k;
+    block_coords(b, K.nb, lane, i, j, k);
+    if (!(i < K.G && j < K.G && k < K.G)) continue;      // padding nodes: velocity defined as zero
+    const int node = (b << 6) + lane;
+    const float p[3] = {(float)i * K.dx, (float)j * K.dx, (float)k * K.dx};
+    float4 q = gv[node];
+    float u[3] = {q.x, q.y, q.z};
+    bool hit = false;
+    for (int c = 0; c < S.n; ++c) hit = field_apply(S.c[c], p, u) || hit;
+    if (hit) gv[node] = make_float4(u[0], u[1], u[2], q.w);
+  }
+}
+
+// adjoint of k_grid_collide_field, in front of k_grid_collide_bwd: gg {dL/du''} -> {dL/du'}, u' the velocity behind the analytic
+// colliders.  u' is recomputed from {mv, m} through grid_velocity and the whole analytic chain A; the velocity field collider c
+// saw is then replayed from u' through the field colliders in front of it (no per-lane history, as in k_grid_collide_bwd).
+__global__ void __launch_bounds__(256) k_grid_collide_field_bwd(const int* __restrict__ list, const int* __restrict__ count,
+                                                                const float4* __restrict__ gm, float4* __restrict__ gg, MpmK K,
+                                                                ColliderSet A, FieldColliderSet S) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int cnt = *count;
+  for (int li = blockIdx.x * 4 + wave; li < cnt; li += gridDim.x * 4) {
+    const int b = list[li];
+    int i, j, k;
+    block_coords(b, K.nb, lane, i, j, k);
+    if (!(i < K.G && j < K.G && k < K.G)) continue;
+    const int node = (b << 6) + lane;
+    const float p[3] = {(float)i * K.dx, (float)j * K.dx, (float)k * K.dx};
+    float n_[3];
+    bool hit = false;
+    for (int c = 0; c < S.n; ++c) hit = field_normal(S.c[c], p, n_) || hit;
+    if (!hit) continue;
+    float u0[3], mk[3];
+    grid_velocity(K, i, j, k, gm[node], u0, mk);
+    u0[0] *= mk[0]; u0[1] *= mk[1]; u0[2] *= mk[2];
+    for (int c = 0; c < A.n; ++c) collide_apply(A.c[c], p, u0);
+    float4 q = gg[node];
+    float g[3] = {q.x, q.y, q.z};
+    for (int c = S.n - 1; c >= 0; --c) {
+      if (!field_normal(S.c[c], p, n_)) continue;      // outside this one: identity, nothing to replay
+      float u[3] = {u0[0], u0[1], u0[2]};
+      for (int e = 0; e < c; ++e) field_apply(S.c[e], p, u);
+      field_adjoint(S.c[c], p, u, g);
+    }
+    gg[node] = make_float4(g[0], g[1], g[2], q.w);
+  }
+}
+
 // mpm.py:432-498 (body: g2p_particle, nm_grid.h)
 __global__ void __launch_bounds__(256, 3) k_g2p(MpmK K, int n, const float* __restrict__ clip, const int* __restrict__ enabled,
                                              const float* x, const float* v, const float* C, const float* F,
@@ -1356,7 +1413,7 @@ __global__ void k_grid_stats(const float4* __restrict__ gm, const int* __restric
 // dense (G,G,G) view of the block-sparse grid, as the reference's arrays read after grid_op: blocks the last substep did
 // not touch hold m = mv = 0 and v = BC(g dt) (the dense sweep of mpm.py:373-429 visits every node)
 __global__ void k_grid_export(MpmK K, const float4* __restrict__ gm, const float4* __restrict__ gv, float* mv, float* m,
-                              float* v, const int* __restrict__ flags, int epoch, ColliderSet S) {
+                              float* v, const int* __restrict__ flags, int epoch, ColliderSet S, FieldColliderSet F) {
   int t = blockIdx.x * blockDim.x + threadIdx.x;
   int G = K.G;
   if (t >= G * G * G) return;
@@ -1370,6 +1427,7 @@ __global__ void k_grid_export(MpmK K, const float4* __restrict__ gm, const float
     w[0] *= mk[0]; w[1] *= mk[1]; w[2] *= mk[2];
     const float p[3] = {(float)i * K.dx, (float)j * K.dx, (float)k * K.dx};
     for (int c = 0; c < S.n; ++c) collide_apply(S.c[c], p, w);      // (the dense sweep would have visited this node too)
+    for (int c = 0; c < F.n; ++c) field_apply(F.c[c], p, w);
     u = make_float4(w[0], w[1], w[2], 0.f);
   }
   if (mv) { mv[3 * t] = q.x; mv[3 * t + 1] = q.y; mv[3 * t + 2] = q.z; }
@@ -1428,6 +1486,7 @@ extern "C" int nm_mpm_create(const nm_mpm_cfg* cfg, nm_mpm** out) {
   h->resident_rec = nullptr; h->resident_epoch = -1;
   h->sh_cnt = h->sh_pos = nullptr;
   h->colliders.n = 0;
+  h->fields.n = 0;
   *out = h;
   return NM_OK;
 }
@@ -1517,21 +1576,35 @@ static int launch_grid_op(nm_mpm* h, void* save, int cap, const int* skip, int32
   NM_LAUNCH_CHECK();
   return NM_OK;
 }
-// colliders behind the grid update (or behind a restore): not launched when the handle holds none
+// colliders behind the grid update (or behind a restore): the analytic ones, then the field colliders; neither kernel is
+// launched when the handle holds none of its kind
 static int launch_grid_collide(nm_mpm* h, hipStream_t s) {
-  if (h->colliders.n == 0) return NM_OK;
   const int now = h->cur;
-  NM_LAUNCH(k_grid_collide, dim3(kSweepGrid), dim3(256), 0, s, (const int*)h->list[now], (const int*)(h->count + now), h->gv, h->k,
-                     h->colliders);
-  NM_LAUNCH_CHECK();
+  if (h->colliders.n != 0) {
+    NM_LAUNCH(k_grid_collide, dim3(kSweepGrid), dim3(256), 0, s, (const int*)h->list[now], (const int*)(h->count + now), h->gv, h->k,
+                       h->colliders);
+    NM_LAUNCH_CHECK();
+  }
+  if (h->fields.n != 0) {
+    NM_LAUNCH(k_grid_collide_field, dim3(kSweepGrid), dim3(256), 0, s, (const int*)h->list[now], (const int*)(h->count + now), h->gv,
+                       h->k, h->fields);
+    NM_LAUNCH_CHECK();
+  }
   return NM_OK;
 }
+// the adjoints in reverse: field colliders first
 static int launch_grid_collide_bwd(nm_mpm* h, hipStream_t s) {
-  if (h->colliders.n == 0) return NM_OK;
   const int now = h->cur;
-  NM_LAUNCH(k_grid_collide_bwd, dim3(kSweepGrid), dim3(256), 0, s, (const int*)h->list[now], (const int*)(h->count + now),
-                     (const float4*)h->gm, h->gg, h->k, h->colliders);
-  NM_LAUNCH_CHECK();
+  if (h->fields.n != 0) {
+    NM_LAUNCH(k_grid_collide_field_bwd, dim3(kSweepGrid), dim3(256), 0, s, (const int*)h->list[now], (const int*)(h->count + now),
+                       (const float4*)h->gm, h->gg, h->k, h->colliders, h->fields);
+    NM_LAUNCH_CHECK();
+  }
+  if (h->colliders.n != 0) {
+    NM_LAUNCH(k_grid_collide_bwd, dim3(kSweepGrid), dim3(256), 0, s, (const int*)h->list[now], (const int*)(h->count + now),
+                       (const float4*)h->gm, h->gg, h->k, h->colliders);
+    NM_LAUNCH_CHECK();
+  }
   return NM_OK;
 }
 static int launch_g2p(nm_mpm* h, int n, const nm_statics* st, const nm_particles* cur, nm_particles* next, hipStream_t s) {
@@ -1930,6 +2003,31 @@ extern "C" int nm_mpm_set_colliders(nm_mpm* h, int32_t n, const nm_collider* hos
   return NM_OK;
 }
 
+// ---- field colliders: the same, for obstacles given as a signed distance field (the phi arrays stay the caller's)
+extern "C" int nm_mpm_set_field_colliders(nm_mpm* h, int32_t n, const nm_field_collider* host) {
+  NM_REQUIRE(h, "field colliders: null handle");
+  NM_REQUIREF(n >= 0 && n <= NM_MAX_FIELD_COLLIDERS, "field colliders: n = %d outside 0..%d", n, NM_MAX_FIELD_COLLIDERS);
+  NM_REQUIRE(n == 0 || host, "field colliders: null array");
+  for (int q = 0; q < n; ++q) {
+    const nm_field_collider& c = host[q];
+    NM_REQUIREF(c.surface == NM_SURFACE_STICKY || c.surface == NM_SURFACE_SLIP || c.surface == NM_SURFACE_FRICTION,
+                "field collider %d: surface: unknown surface %d", q, c.surface);
+    NM_REQUIREF(c.friction >= 0.f && finite1(c.friction), "field collider %d: friction: must not be negative", q);
+    NM_REQUIREF(finite3(c.velocity), "field collider %d: velocity: three finite numbers expected", q);
+    NM_REQUIREF(finite3(c.origin), "field collider %d: origin: three finite numbers expected", q);
+    NM_REQUIREF(c.spacing > 0.f && finite1(c.spacing), "field collider %d: spacing: must be positive", q);
+    NM_REQUIREF(c.dims[0] >= 2 && c.dims[1] >= 2 && c.dims[2] >= 2, "field collider %d: dims: every lattice size must be >= 2", q);
+    const int64_t lim = (int64_t)1 << 27;
+    NM_REQUIREF(c.dims[0] <= lim && c.dims[1] <= lim && (int64_t)c.dims[0] * c.dims[1] <= lim &&
+                    (int64_t)c.dims[0] * c.dims[1] * c.dims[2] <= lim,
+                "field collider %d: dims: more than 2^27 nodes", q);
+    NM_REQUIREF(c.phi != nullptr, "field collider %d: phi: null pointer", q);
+  }
+  h->fields.n = n;
+  for (int q = 0; q < n; ++q) h->fields.c[q] = host[q];
+  return NM_OK;
+}
+
 extern "C" int nm_mpm_grid_stats(nm_mpm* h, int32_t* active_blocks, int32_t* nodes_with_mass, void* stream) {
   NM_REQUIRE(h, "null handle");
   hipStream_t s = (hipStream_t)stream;
@@ -1949,7 +2047,7 @@ extern "C" int nm_mpm_grid_export(nm_mpm* h, float* mv, float* m, float* v, void
   NM_REQUIRE(h, "null handle");
   int G = h->k.G;
   NM_LAUNCH(k_grid_export, dim3(nm_div_up((int64_t)G * G * G, 256)), dim3(256), 0, (hipStream_t)stream, h->k,
-                     h->gm, h->gv, mv, m, v, h->flags, h->epoch, h->colliders);
+                     h->gm, h->gv, mv, m, v, h->flags, h->epoch, h->colliders, h->fields);
   NM_LAUNCH_CHECK();
   return NM_OK;
 }

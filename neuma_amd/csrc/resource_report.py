@@ -24,6 +24,6 @@ for src in srcs:
         if "rocprim" in k:
             continue
         name = subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip()
-        name = re.sub(r"\(.*", "", name)[:40]
+        name = re.sub(r"\(.*", "", name.replace("(anonymous namespace)::", ""))[:40]
         print(f"  {name:40s} vgpr {v.get('VGPRs',0):4d} agpr {v.get('AGPRs',0):4d} sgpr {v.get('SGPRs',0):4d} "
               f"spillV {v.get('VGPRs Spill',0):3d} scratch {v.get('ScratchSize',0):4d} lds {v.get('LDS Size',0):6d} occ {v.get('Occupancy',0)}")

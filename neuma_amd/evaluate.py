@@ -29,7 +29,7 @@ from .config import Cfg, load_config
 from .export import save_frame
 from .finetune import particle_init_data, setup
 from .sim import MPMForwardSim, MPMModelBuilder, MPMStateInitializer, MPMStaticsInitializer
-from .sim.colliders import describe as describe_colliders
+from .sim.colliders import describe as describe_colliders, describe_fields as describe_field_colliders
 from .render.transform_utils import rotate_shs_by_deformation
 from .tune import compute_bindings_F, compute_bindings_xyz, denormalize_points_helper_func, diff_rasterization
 
@@ -120,11 +120,13 @@ def evaluate(cfg: Cfg, on_frame=None):
     draw_styles = None
     if collider_draw.wanted(cfg, cfg.sim):
         if model.colliders:
-            draw_styles = collider_draw.parse_styles(cfg.sim.get("colliders"))
+            draw_styles = collider_draw.parse_styles(list(cfg.sim.get("colliders"))[:len(model.colliders)])      # (mesh entries follow them)
         else:
             print("draw_colliders: sim.colliders is empty, nothing to draw")
     if model.colliders:
         print(describe_colliders(model.colliders, drawn=draw_styles is not None))
+    if model.field_colliders:
+        print(describe_field_colliders(model.field_colliders, draw_wanted=collider_draw.wanted(cfg, cfg.sim)))
     sim = MPMForwardSim(model)
     state_initializer, statics_initializer = MPMStateInitializer(model), MPMStaticsInitializer(model)
     init_data = particle_init_data(cfg, eval_steps)

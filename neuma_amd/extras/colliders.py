@@ -11,15 +11,19 @@ velocity, n the outward normal, w = u - v_c and vn = w.n:
     slip      u' = u - vn n                               if vn < 0, else u
     friction  u' = v_c + max(0, 1 + mu vn / |vt|) vt       if vn < 0 (vt = w - vn n; u' = v_c where vt = 0), else u
 
-Colliders are applied in list order.  No reference counterpart.  Not on the product path: nothing here is called by a
+Colliders are applied in list order.  A FieldCollider (sim/colliders.py: a signed distance field phi on a lattice, e.g. of a mesh)
+takes the same response with the geometry of `field_phi_normal`: trilinear phi in the cell that holds the node, inside iff
+phi < 0, normal = the analytic gradient of that interpolant (apply_field_collider; prose: include/neuma_hip.h "Field colliders").
+No reference counterpart.  Not on the product path: nothing here is called by a
 simulation, and nothing here imports the test oracle.
 """
 from typing import Sequence, Tuple
 
+import numpy as np
 import torch
 from torch import Tensor
 
-from ..sim.colliders import Box, Plane, Sphere
+from ..sim.colliders import Box, FieldCollider, Plane, Sphere
 
 
 def node_positions(num_grids: int, dtype=torch.float64) -> Tensor:
@@ -64,12 +68,58 @@ def sdf_normal(c, p: Tensor) -> Tuple[Tensor, Tensor]:
     raise TypeError(f"not a collider: {c!r}")
 
 
+def field_phi_normal(c: FieldCollider, p: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """(inside (M,) bool, phi (M,), n (M, 3)) of a field collider at the points p (M, 3), in p's dtype: q = (p - origin) / spacing;
+    outside unless 0 <= q_a <= dims_a - 1 on every axis (NaN: outside); cell i = min(floor(q), dims - 2), t = q - i; phi = the
+    trilinear interpolant (along z, then y, then x), n = its gradient in t, normalised (+x where it vanishes).  phi and n are only
+    meaningful on the lattice."""
+    dt = p.dtype
+    f = (c.phi.detach().cpu() if torch.is_tensor(c.phi) else torch.from_numpy(np.array(c.phi))).to(dt)
+    dims = torch.tensor(c.dims, dtype=torch.int64)
+    q = (p - torch.tensor(c.origin, dtype=dt)) / torch.tensor(c.spacing, dtype=dt)
+    on = ((q >= 0) & (q <= (dims - 1).to(dt))).all(-1)
+    qs = torch.where(on[:, None], q, torch.zeros_like(q))
+    fl = torch.minimum(qs.floor(), (dims - 2).to(dt))
+    i = fl.long()
+    t = qs - fl
+    corner = {(a, b, e): f[i[:, 0] + a, i[:, 1] + b, i[:, 2] + e] for a in (0, 1) for b in (0, 1) for e in (0, 1)}
+    tx, ty, tz = t[:, 0], t[:, 1], t[:, 2]
+    d = {(a, b): corner[a, b, 1] - corner[a, b, 0] for a in (0, 1) for b in (0, 1)}      # z differences
+    a_ = {k: corner[k[0], k[1], 0] + tz * d[k] for k in d}
+    e0, e1 = a_[0, 1] - a_[0, 0], a_[1, 1] - a_[1, 0]
+    b0, b1 = a_[0, 0] + ty * e0, a_[1, 0] + ty * e1
+    gx = b1 - b0
+    phi = b0 + tx * gx
+    gy = e0 + tx * (e1 - e0)
+    z0, z1 = d[0, 0] + ty * (d[0, 1] - d[0, 0]), d[1, 0] + ty * (d[1, 1] - d[1, 0])
+    gz = z0 + tx * (z1 - z0)
+    g = torch.stack([gx, gy, gz], dim=-1)
+    l2 = (gx * gx + gy * gy) + gz * gz
+    ex = torch.tensor([1.0, 0.0, 0.0], dtype=dt).expand_as(g)
+    n = torch.where((l2 > 0)[:, None], g / torch.where(l2 > 0, l2, torch.ones_like(l2)).sqrt()[:, None], ex)
+    return on & (phi < 0), phi, n
+
+
+def apply_field_collider(c: FieldCollider, p: Tensor, u: Tensor) -> Tensor:
+    """One field collider's response at the nodes p (M, 3) with velocities u (M, 3), in u's dtype."""
+    with torch.no_grad():
+        inside, _, n = field_phi_normal(c, p.to(u.dtype))
+    return _respond(c, inside, n, u)
+
+
 def apply_collider(c, p: Tensor, u: Tensor) -> Tensor:
     """One collider's response at the nodes p (M, 3) with velocities u (M, 3)."""
-    dt = u.dtype
+    if isinstance(c, FieldCollider):
+        return apply_field_collider(c, p, u)
     with torch.no_grad():
-        sdf, n = sdf_normal(c, p.to(dt))
+        sdf, n = sdf_normal(c, p.to(u.dtype))
         inside = sdf < 0
+    return _respond(c, inside, n, u)
+
+
+def _respond(c, inside: Tensor, n: Tensor, u: Tensor) -> Tensor:
+    """The sticky / slip / friction law at the nodes `inside`, given the outward normals n."""
+    dt = u.dtype
     vc = torch.as_tensor(c.velocity, dtype=dt).expand_as(u)
     if c.surface == "sticky":
         new = vc

@@ -41,7 +41,7 @@ from .infer import SceneObject, simulate_objects
 from .material import InvariantFullMetaElasticity, InvariantFullMetaPlasticity, build as build_material
 from .prepare import prepare_simulation_data
 from .sim import MPMInitData, MPMModelBuilder
-from .sim.colliders import describe as describe_colliders
+from .sim.colliders import describe as describe_colliders, describe_fields as describe_field_colliders
 
 RESULT = "results"
 
@@ -175,11 +175,13 @@ def inference(cfg: Cfg, on_frame=None):
     draw_styles = None
     if collider_draw.wanted(cfg, cfg.sim):
         if model.colliders:
-            draw_styles = collider_draw.parse_styles(cfg.sim.get("colliders"))
+            draw_styles = collider_draw.parse_styles(list(cfg.sim.get("colliders"))[:len(model.colliders)])      # (mesh entries follow them)
         else:
             print("draw_colliders: sim.colliders is empty, nothing to draw")
     if model.colliders:
         print(describe_colliders(model.colliders, drawn=draw_styles is not None))
+    if model.field_colliders:
+        print(describe_field_colliders(model.field_colliders, draw_wanted=collider_draw.wanted(cfg, cfg.sim)))
     if cfg.get("dataset_path") is not None:
         cfg.video_data.data.path = cfg.dataset_path
         print(f"Rewrite video dataset path to\n\t{cfg.dataset_path}")

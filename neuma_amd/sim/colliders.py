@@ -11,15 +11,29 @@ fp64 restatement: neuma_amd/extras/colliders.py; kernels: csrc/nm_collide.h + k_
 
 parse_colliders turns such a list into Plane / Sphere / Box objects (normals normalised and rotations built in fp64), with
 the validation - and the messages - of nm_mpm_set_colliders; pack() makes the ctypes array that call takes.
+
+Mesh colliders: a closed triangle mesh as an obstacle, through its signed distance field on a lattice (neuma_amd/mesh_sdf.py;
+response: include/neuma_hip.h "Field colliders", csrc/nm_collide_field.h, extras/colliders.py apply_field_collider).
+
+        - {type: mesh, path: bowl.obj, scale: 0.3, euler_xyz_deg: [0, 0, 15], translate: [0.5, 0.2, 0.5],
+           resolution: 64, surface: friction, friction: 0.4, velocity: [0, 0, 0]}
+
+The mesh (`path`: .obj / .ply, or `verts` / `tris` arrays from code) is mapped by p_s = scale R p_mesh + translate in fp64 on
+the host; `resolution` cells along the longest axis of its box (or a `spacing`), `margin_cells` (2) cells of margin.  Mesh entries
+come after all analytic entries (list order is the order of application, and field colliders act behind the analytic ones), at
+most MAX_FIELD_COLLIDERS of them.  parse_colliders returns them as MeshCollider objects behind the analytic ones; a model builds
+each one's field once (MeshCollider.build -> FieldCollider, which is what nm_mpm_set_field_colliders takes: pack_fields).  A
+FieldCollider can also be made from any signed distance field directly.  pack() stays what it was: analytic colliders only.
 """
 import ctypes as C
 import math
 from dataclasses import dataclass, field, replace
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 from .. import _lib as L
 
 MAX_COLLIDERS = 8
+MAX_FIELD_COLLIDERS = 4
 SHAPES = {"plane": 0, "sphere": 1, "box": 2}
 SURFACES = {"sticky": 0, "slip": 1, "friction": 2}
 _IDENTITY = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0)
@@ -127,6 +141,109 @@ class Box(_Collider):
         return replace(self, center=tuple(p + dt * v for p, v in zip(self.center, self.velocity)))
 
 
+@dataclass(frozen=True, eq=False)
+class FieldCollider(_Collider):
+    """An obstacle given as a signed distance field phi (nx, ny, nz; negative inside) on the lattice origin + index * spacing, in
+    simulation coordinates.  phi: an fp32 tensor on the model's device for a simulation (the model keeps it alive); any array for
+    the fp64 definition (extras/colliders.py).  origin is the position of node (0,0,0) NOW; `source`: the MeshCollider it was
+    built from, if any."""
+    phi: object = None
+    origin: Tuple[float, float, float] = (0.0, 0.0, 0.0)
+    spacing: float = 0.0
+    dims: Tuple[int, int, int] = (0, 0, 0)
+    source: Optional["MeshCollider"] = None
+
+    def __post_init__(self) -> None:
+        self._check_common()
+        object.__setattr__(self, "origin", _vec3(self.origin, "origin"))
+        if not (float(self.spacing) > 0.0 and math.isfinite(float(self.spacing))):
+            raise ValueError(f"spacing: must be positive (got {self.spacing})")
+        object.__setattr__(self, "spacing", float(self.spacing))
+        dims = tuple(int(d) for d in self.dims)
+        if len(dims) != 3 or min(dims) < 2:
+            raise ValueError(f"dims: every lattice size must be >= 2 (got {self.dims})")
+        if dims[0] * dims[1] * dims[2] > (1 << 27):
+            raise ValueError(f"dims: more than 2^27 nodes ({dims})")
+        object.__setattr__(self, "dims", dims)
+        if self.phi is None or tuple(self.phi.shape) != dims:
+            raise ValueError(f"phi: an array of shape {dims} expected")
+
+    def advanced(self, dt: float) -> "FieldCollider":
+        return replace(self, origin=tuple(p + dt * v for p, v in zip(self.origin, self.velocity)))
+
+
+@dataclass(frozen=True, eq=False)
+class MeshCollider(_Collider):
+    """A closed triangle mesh as an obstacle: verts (n, 3) fp64 ALREADY in simulation coordinates, tris (m, 3).  build() makes the
+    FieldCollider a model steps against."""
+    verts: object = None
+    tris: object = None
+    path: Optional[str] = None
+    resolution: int = 64
+    spacing: Optional[float] = None
+    margin_cells: int = 2
+
+    def __post_init__(self) -> None:
+        import numpy as np
+        from ..extras import mesh_sdf
+        self._check_common()
+        v = np.asarray(self.verts, dtype=np.float64)
+        if v.ndim != 2 or v.shape[1] != 3 or len(v) == 0 or not np.isfinite(v).all():
+            raise ValueError("verts: an (n, 3) array of finite numbers expected")
+        t = np.asarray(self.tris)
+        if t.ndim != 2 or t.shape[1] != 3 or not np.issubdtype(t.dtype, np.integer):
+            raise ValueError("tris: an (m, 3) array of vertex indices expected")
+        object.__setattr__(self, "verts", v)
+        object.__setattr__(self, "tris", mesh_sdf.check_closed_mesh(v, t))          # ValueError: open (edge count) / inverted
+        if self.spacing is None and not int(self.resolution) >= 1:
+            raise ValueError(f"resolution: must be >= 1 (got {self.resolution})")
+        if self.spacing is not None and not (float(self.spacing) > 0.0 and math.isfinite(float(self.spacing))):
+            raise ValueError(f"spacing: must be positive (got {self.spacing})")
+        if not int(self.margin_cells) >= 0:
+            raise ValueError(f"margin_cells: must not be negative (got {self.margin_cells})")
+        mesh_sdf.field_lattice(v, self.spacing, self.resolution, self.margin_cells)   # ValueError: a lattice beyond 2^27 nodes
+
+    def build(self, device) -> FieldCollider:
+        """The signed distance field on `device` (a GPU: nm_mesh_distance + nm_points_in_mesh; "cpu": numpy fp64)."""
+        from .. import mesh_sdf
+        f = mesh_sdf.build_mesh_field(self.verts, self.tris, self.spacing, self.resolution, self.margin_cells, device)
+        return FieldCollider(surface=self.surface, friction=self.friction, velocity=self.velocity, phi=f.phi, origin=f.origin,
+                             spacing=f.spacing, dims=f.dims, source=self)
+
+
+def _mesh_collider(node, common) -> MeshCollider:
+    import numpy as np
+    path, verts, tris = node.get("path"), node.get("verts"), node.get("tris")
+    if (path is None) == (verts is None or tris is None):
+        raise ValueError("path: give either a mesh file (path) or verts and tris arrays")
+    if path is not None:
+        from ..extras import mesh_sampling
+        low = str(path).lower()
+        if low.endswith(".obj"):
+            verts, tris = mesh_sampling.read_obj_mesh(path)
+        elif low.endswith(".ply"):
+            verts, tris = mesh_sampling.read_ply_mesh(path)
+        else:
+            raise ValueError(f"path: an .obj or .ply mesh expected, got {path!r}")
+    v = np.asarray(verts, dtype=np.float64)
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError("verts: an (n, 3) array of finite numbers expected")
+    scale = float(node.get("scale", 1.0))
+    if not (scale > 0.0 and math.isfinite(scale)):
+        raise ValueError(f"scale: must be positive (got {node.get('scale')})")
+    R = np.asarray(euler_xyz_deg_to_rot(node.get("euler_xyz_deg", (0.0, 0.0, 0.0))), dtype=np.float64).reshape(3, 3)
+    tr = np.asarray(_vec3(node.get("translate", (0.0, 0.0, 0.0)), "translate"), dtype=np.float64)
+    spacing = node.get("spacing")
+    return MeshCollider(verts=scale * (v @ R.T) + tr, tris=tris, path=None if path is None else str(path),
+                        resolution=int(node.get("resolution", 64)), spacing=None if spacing is None else float(spacing),
+                        margin_cells=int(node.get("margin_cells", 2)), **common)
+
+
+def is_field(c) -> bool:
+    """a mesh / field collider (applied behind the analytic ones) rather than a Plane / Sphere / Box"""
+    return isinstance(c, (MeshCollider, FieldCollider))
+
+
 def euler_xyz_deg_to_rot(angles) -> Tuple[float, ...]:
     """R = Rz(c) Ry(b) Rx(a) for angles (a, b, c) in degrees about the fixed x, y, z axes, row-major, in fp64."""
     a, b, c = (math.radians(v) for v in _vec3(angles, "euler_xyz_deg"))
@@ -137,7 +254,8 @@ def euler_xyz_deg_to_rot(angles) -> Tuple[float, ...]:
 
 
 def parse_collider(node, index: int = 0):
-    """One entry of `sim.colliders` (a dict; config nodes are dicts) -> Plane / Sphere / Box.  Errors name the entry and the field."""
+    """One entry of `sim.colliders` (a dict; config nodes are dicts) -> Plane / Sphere / Box / MeshCollider.  Errors name the entry
+    and the field."""
     if isinstance(node, _Collider):
         return node
     kind = node.get("type")
@@ -154,17 +272,34 @@ def parse_collider(node, index: int = 0):
                 raise ValueError("rot: give either euler_xyz_deg or rot, not both")
             rot = euler_xyz_deg_to_rot(euler) if euler is not None else (_IDENTITY if rot is None else rot)
             return Box(center=node.get("center", (0.0, 0.0, 0.0)), half=node.get("half", (0.0, 0.0, 0.0)), rot=rot, **common)
-        raise ValueError(f"shape: unknown shape {kind!r} (one of {sorted(SHAPES)})")
+        if kind == "mesh":
+            return _mesh_collider(node, common)
+        raise ValueError(f"shape: unknown shape {kind!r} (one of {sorted(SHAPES) + ['mesh']})")
     except ValueError as e:
         raise ValueError(f"collider {index}: {e}") from None
 
 
 def parse_colliders(nodes) -> List:
-    """A `sim.colliders` list (dicts / config nodes / collider objects) -> validated collider objects, in order."""
+    """A `sim.colliders` list (dicts / config nodes / collider objects) -> validated collider objects, in order: the analytic ones
+    (at most MAX_COLLIDERS), then the mesh / field colliders (at most MAX_FIELD_COLLIDERS).  A mesh entry in front of an analytic
+    one raises ValueError naming the entry: list order is the order of application."""
     nodes = [] if nodes is None else list(nodes)
-    if len(nodes) > MAX_COLLIDERS:
-        raise ValueError(f"colliders: n = {len(nodes)} outside 0..{MAX_COLLIDERS}")
+    kinds = [is_field(n) or (not isinstance(n, _Collider) and n.get("type") == "mesh") for n in nodes]
+    n_analytic, n_field = kinds.count(False), kinds.count(True)
+    if n_analytic > MAX_COLLIDERS:
+        raise ValueError(f"colliders: n = {n_analytic} outside 0..{MAX_COLLIDERS}")
+    if n_field > MAX_FIELD_COLLIDERS:
+        raise ValueError(f"colliders: {n_field} mesh colliders, at most {MAX_FIELD_COLLIDERS}")
+    for i, k in enumerate(kinds):
+        if k and not all(kinds[i:]):
+            raise ValueError(f"collider {i}: a mesh collider in front of an analytic one (mesh entries come after all plane / sphere / "
+                             "box entries: they are applied behind them)")
     return [parse_collider(n, i) for i, n in enumerate(nodes)]
+
+
+def split(colliders: Sequence) -> Tuple[List, List]:
+    """(analytic colliders, mesh / field colliders) of a parsed list, each in order"""
+    return [c for c in colliders if not is_field(c)], [c for c in colliders if is_field(c)]
 
 
 def pack(colliders: Sequence):
@@ -185,6 +320,37 @@ def pack(colliders: Sequence):
         out.half = (C.c_float * 3)(*(c.half if isinstance(c, Box) else (0.0, 0.0, 0.0)))
         out.rot = (C.c_float * 9)(*(c.rot if isinstance(c, Box) else _IDENTITY))
     return arr
+
+
+def pack_fields(fields: Sequence):
+    """ctypes array of nm_field_collider for nm_mpm_set_field_colliders (None for an empty list).  Every phi must be a contiguous
+    fp32 tensor on the GPU; the caller keeps the tensors alive while the handle holds the set."""
+    if len(fields) > MAX_FIELD_COLLIDERS:
+        raise ValueError(f"field colliders: n = {len(fields)} outside 0..{MAX_FIELD_COLLIDERS}")
+    if not fields:
+        return None
+    arr = (L.nm_field_collider * len(fields))()
+    for out, c in zip(arr, fields):
+        out.surface = SURFACES[c.surface]
+        out.friction = c.friction
+        out.velocity = (C.c_float * 3)(*c.velocity)
+        out.origin = (C.c_float * 3)(*c.origin)
+        out.spacing = c.spacing
+        out.dims = (C.c_int32 * 3)(*c.dims)
+        out.phi = L.ptr(c.phi)
+    return arr
+
+
+def describe_fields(fields: Sequence, draw_wanted: bool = False) -> str:
+    """One line per mesh / field collider: path, triangle count, lattice, surface."""
+    lines = [f"mesh colliders: {len(fields)}" + (" (mesh colliders are not drawn in renders)" if draw_wanted else "")]
+    for i, c in enumerate(fields):
+        src = c if isinstance(c, MeshCollider) else c.source
+        what = f"mesh path={src.path} triangles={len(src.tris)}" if src is not None else "field"
+        lat = f" lattice={c.dims[0]}x{c.dims[1]}x{c.dims[2]} spacing={c.spacing:.6g}" if isinstance(c, FieldCollider) else ""
+        surf = c.surface + (f" mu={c.friction}" if c.surface == "friction" else "")
+        lines.append(f"  [{i}] {what}{lat} surface={surf} velocity={c.velocity}")
+    return "\n".join(lines)
 
 
 def describe(colliders: Sequence, drawn: bool = False) -> str:

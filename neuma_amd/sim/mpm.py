@@ -6,7 +6,7 @@ Mirrors the public surface of /root/reference/modules/nclaw/sim/mpm.py:
 The Warp structs become plain holders of torch tensors; the kernels (p2g / grid_op / g2p and their
 adjoints) live in csrc/nm_mpm.hip and are reached through nm_mpm_forward / nm_mpm_backward.
 """
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from pathlib import Path
 from typing import Any, Optional, Sequence, Union
 import ctypes as C
@@ -207,13 +207,14 @@ class MPMModel(Model):
         self._cache_blocks = None
         self.exchange = None        # set by shard(): this model steps one rank's share of the particles
         self._colliders = []        # set_colliders(): rigid obstacles of the per-operator path (sim/colliders.py)
+        self._field_colliders = []  # ... its mesh / field colliders (FieldCollider objects: each holds its phi tensor alive)
 
     def shard(self, group=None, cap=None, cap_shared=None, cap_dil=None, cap_frame=None):
         """Make this model one rank of a particle-sharded simulation (sim/shard.py): every forward / backward sums the
         grid blocks it shares with other ranks over `group`.  Capacities default to 1.5x what the first substep needs
         (cap, cap_shared: per-substep lists and grid cache records; cap_dil, cap_frame: the fused roll-out's frame-level
         neighbourhood and exchange lists)."""
-        if self._colliders:
+        if self._colliders or self._field_colliders:
             raise L.NeumaHipError("colliders: per-operator path only (a model with colliders cannot be sharded)")
         from .shard import GridExchange
         self.exchange = GridExchange(self, group, cap, cap_shared, cap_dil, cap_frame)
@@ -256,30 +257,52 @@ class MPMModel(Model):
     # -- colliders (no reference counterpart; sim/colliders.py)
     @property
     def colliders(self):
-        """The colliders this model steps against (Plane / Sphere / Box objects, in the order they are applied)."""
+        """The analytic colliders this model steps against (Plane / Sphere / Box objects, in the order they are applied)."""
         return list(self._colliders)
+
+    @property
+    def field_colliders(self):
+        """The mesh / field colliders (FieldCollider objects with their phi on the model's device), applied behind `colliders`, in
+        order.  `origin` is where each lattice sits now (step_colliders moves it)."""
+        return list(self._field_colliders)
 
     def set_colliders(self, colliders) -> None:
         """Replace the model's colliders (dicts as in the `sim.colliders` config list, or collider objects; [] / None removes
         them).  Host-only: may be called between any two substeps.  Colliders act on MPMModel.forward / backward (the per-operator
-        path); the fused roll-out, forward_extra and sharded models refuse them."""
+        path); the fused roll-out, forward_extra and sharded models refuse them.  `type: mesh` entries / MeshCollider objects
+        (behind all analytic ones) have their signed distance field built here, once, on the model's device; FieldCollider objects
+        are taken as they are (phi is moved to the device if it is elsewhere)."""
         if self.exchange is not None:
             raise L.NeumaHipError("colliders: per-operator path only (set_colliders on a sharded model)")
-        self._colliders = _colliders.parse_colliders(colliders)
+        analytic, fields = _colliders.split(_colliders.parse_colliders(colliders))
+        built = []
+        for c in fields:
+            if isinstance(c, _colliders.MeshCollider):
+                c = c.build(self.device)
+            if not (torch.is_tensor(c.phi) and c.phi.device == self.device and c.phi.dtype == torch.float32 and c.phi.is_contiguous()):
+                phi = c.phi if torch.is_tensor(c.phi) else torch.from_numpy(np.array(c.phi))
+                c = replace(c, phi=phi.to(device=self.device, dtype=torch.float32).contiguous())
+            built.append(c)
+        self._colliders, self._field_colliders = analytic, built
         if self._handle is not None:      # (a handle created later takes them along: handle())
             self._upload_colliders()
 
     def _upload_colliders(self) -> None:
         arr = _colliders.pack(self._colliders)
         L.check(L.lib().nm_mpm_set_colliders(self._handle, len(self._colliders), arr), "nm_mpm_set_colliders")
+        arr = _colliders.pack_fields(self._field_colliders)
+        L.check(L.lib().nm_mpm_set_field_colliders(self._handle, len(self._field_colliders), arr), "nm_mpm_set_field_colliders")
 
     def step_colliders(self) -> None:
-        """Advance the centres of the moving colliders by velocity * dt (one substep) and re-upload; nothing when none moves."""
-        if not any(c.moving for c in self._colliders):
+        """Advance the centres of the moving colliders - and the lattice origins of the moving field colliders - by velocity * dt
+        (one substep) and re-upload; nothing when none moves."""
+        if not any(c.moving for c in self._colliders + self._field_colliders):
             return
         dt = float(self.constant.dt)
         self._colliders = [c.advanced(dt) if c.moving else c for c in self._colliders]
-        self._upload_colliders()
+        self._field_colliders = [c.advanced(dt) if c.moving else c for c in self._field_colliders]
+        if self._handle is not None:      # (a handle created later takes them along: handle())
+            self._upload_colliders()
 
     def __del__(self):
         try:
