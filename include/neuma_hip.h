@@ -288,6 +288,44 @@ int nm_collider_hide(const float* campos, const float* map_a, const float* map_b
 int nm_collider_compose(const struct nm_raster_cfg* cfg, const float* img_all, const float* rgb_front, const float* a_front,
                         const float* shade, const int32_t* hit, float* out, void* stream);
 
+/* Drawing mesh colliders (no reference counterpart; kernels: k_field_cast / k_field_hide in csrc/nm_draw.hip, the trace:
+ * csrc/nm_field_ray.h; the same definition in fp64: neuma_amd/extras/mesh_draw.py; prose: DESIGN.md section 7).  Two IN-OUT passes
+ * behind nm_collider_cast / nm_collider_hide; nm_collider_compose needs only hit >= 0 and stays as it is.
+ * Drawn solid of a field collider: the zero level set's inside, {phi < 0}, of the trilinearly interpolated phi ("Field colliders"
+ *   above), cut by the lattice box [origin, origin + (dims - 1) spacing] and by the unit cube - the solid the simulator collides
+ *   with, at the lattice's resolution; `origin` is where the collider is NOW.
+ * Rays: exactly those of "Drawing colliders": o_s = (o_r - b) / a, the un-normalised d_s = d_r / a (t is the render-space
+ *   distance), L = |d_s|.
+ * Interval: [t0, t1] = t >= 0, the three slabs of the unit cube, the three slabs of the lattice box; t0 is the largest entry
+ *   (of equal entries the first in the order t >= 0, cube x, y, z, lattice x, y, z), t1 the smallest exit.  With t_end =
+ *   min(t1, the t already in the buffer): t0 >= t_end is a miss.
+ * Sample: phi(t) is the interpolant at o_s + t d_s, q = (p - origin) / spacing, cell i_a = max(min(floor(q_a), dims_a - 2), 0)
+ *   (a point a rounding error outside the lattice extrapolates its border cell), fraction q - i.
+ * Face hit: phi(t0) < 0: the hit is at t0 and the normal is that of the slab that gave t0; t0 = 0 (the camera is inside the
+ *   solid): the normal faces the camera, n_r.l = 1.
+ * March: tau = 1e-3 spacing; at most 192 times: phi(t) <= tau -> converged; otherwise t += max(phi, tau) / L, and t >= t_end is
+ *   a miss.  A ray still marching after 192 steps is a miss.  (Step factor 1: phi is a distance in simulation units.)
+ * Polish: three Newton steps along the ray, t -= phi / (grad . d_s) with the analytic gradient of the interpolant in simulation
+ *   units (divided by spacing) in the cell that holds the point, each taken only while grad . d_s < 0; t is kept in [t0, t1].
+ * Normal and shade: n_s = grad / |grad| at the final t (+x where the gradient vanishes), n_r = normalize(n_s / a), rgb = color *
+ *   (0.35 + 0.65 max(0, n_r . -d_r)); a style's checker is ignored.
+ * Merge: a field hit replaces a pixel only where its final t is strictly smaller than the t in the buffer - analytic colliders win
+ *   ties, and among fields the first in list order; hit becomes hit_base + j (the caller passes the number of analytic colliders).
+ *   A pixel no field changes is not written.
+ * Occlusion per Gaussian: the same interval, face hit and march on the segment o_s + u (mean_s - o_s) with t_end = min(t1, 1) (no
+ *   polish); a Gaussian is hidden when that hits, or when the mean lies in the unit cube and inside the field ("Field colliders":
+ *   on the lattice and phi(mean) < 0).  Hidden Gaussians get opacity_front = 0 and hidden = 1; the others are not written. */
+/* t, shade, hit: what nm_collider_cast has written (n = 0 there is valid and writes +inf / 0 / -1), updated in place.  n = 0 is a
+ * valid no-op.  NM_ERR_INVALID, naming the field: the map, style, camera and inv_proj checks of nm_collider_cast, n outside
+ * 0..NM_MAX_FIELD_COLLIDERS, a negative hit_base, and nm_mpm_set_field_colliders' checks (surface, friction, velocity, origin,
+ * spacing, dims, phi) as "field collider <j>: <field>: ...". */
+int nm_collider_cast_field(const struct nm_raster_cfg* cfg, const double* inv_proj, const float* map_a, const float* map_b, int32_t n,
+                           const nm_field_collider* fields, const nm_collider_style* styles, int32_t hit_base, float* t, float* shade,
+                           int32_t* hit, void* stream);
+/* opacity_front (K,1) and hidden (K uint8, may be NULL): what nm_collider_hide has written, updated in place.  Same validation. */
+int nm_collider_hide_field(const float* campos, const float* map_a, const float* map_b, int32_t n, const nm_field_collider* fields,
+                           int32_t k, const float* means3D, float* opacity_front, uint8_t* hidden, void* stream);
+
 /* ------------------------------------------------------------------ SVD (modules/nclaw/warp/svd.py) */
 
 /* SVDFunction.forward / batch_svd, svd.py:12-38, 61-96.  F (N,3,3) -> U (N,3,3), sigma (N,3), Vh (N,3,3);

@@ -131,6 +131,10 @@ SIGNATURES = {
     "nm_collider_hide": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), _I32, C.POINTER(nm_collider), _I32,
                                   _P, _P, _P, _P, _P]),
     "nm_collider_compose": (C.c_int, [C.POINTER(nm_raster_cfg), _P, _P, _P, _P, _P, _P, _P]),
+    "nm_collider_cast_field": (C.c_int, [C.POINTER(nm_raster_cfg), C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_float), _I32,
+                                        C.POINTER(nm_field_collider), C.POINTER(nm_collider_style), _I32, _P, _P, _P, _P]),
+    "nm_collider_hide_field": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), _I32,
+                                        C.POINTER(nm_field_collider), _I32, _P, _P, _P, _P]),
     "nm_svd3_fwd": (C.c_int, [_I32, _P, _P, _P, _P, _P]),
     "nm_svd3_bwd": (C.c_int, [_I32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nm_material_fwd": (C.c_int, [_I32, _I32, _F, _P, C.POINTER(nm_mlp), _P, _P]),

@@ -12,6 +12,11 @@ Gaussians' opacities zeroed (`render_front`) and three small launches.
 
 `color` (rgb in 0..1) defaults to a fixed palette by index, `checker` (cell size in simulation units, planes only; 0 = plain) to
 0.125.  Occlusion is per Gaussian: one whose centre is behind or inside a drawn solid is dropped as a whole.  Not differentiated.
+
+Mesh colliders (`type: mesh`) are drawn with `draw_mesh_colliders: true` / --draw_mesh_colliders, which implies draw_colliders: a
+sphere trace of each collider's signed distance field (k_field_cast / k_field_hide, csrc/nm_field_ray.h; definition:
+include/neuma_hip.h "Drawing mesh colliders", fp64: neuma_amd/extras/mesh_draw.py) merged into the analytic cast's buffers - what
+is drawn is the solid the simulator collides with, at the lattice's resolution.  Mesh entries take `color`; `checker` is ignored.
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -22,7 +27,8 @@ from torch import Tensor
 
 from . import _lib as L
 from .extras import collider_draw as X
-from .sim.colliders import MAX_COLLIDERS, Plane, pack
+from .extras import mesh_draw as XM
+from .sim.colliders import MAX_COLLIDERS, MAX_FIELD_COLLIDERS, Plane, pack, pack_fields
 
 IDENTITY = X.IDENTITY
 PALETTE = ((0.78, 0.78, 0.74), (0.85, 0.33, 0.25), (0.25, 0.52, 0.85), (0.35, 0.72, 0.40),
@@ -62,6 +68,24 @@ def parse_styles(nodes) -> List[Style]:
     if len(nodes) > MAX_COLLIDERS:
         raise ValueError(f"colliders: n = {len(nodes)} outside 0..{MAX_COLLIDERS}")
     return [parse_style(n, i) for i, n in enumerate(nodes)]
+
+
+def parse_mesh_styles(nodes, first_index: int = 0) -> List[Style]:
+    """The mesh entries of a `sim.colliders` list (those behind its `first_index` analytic entries) -> one Style per entry.  Only
+    `color` is read - the palette default goes by the index in the whole list - and `checker` is ignored."""
+    nodes = [] if nodes is None else list(nodes)
+    if len(nodes) > MAX_FIELD_COLLIDERS:
+        raise ValueError(f"colliders: {len(nodes)} mesh colliders, at most {MAX_FIELD_COLLIDERS}")
+    out = []
+    for i, n in enumerate(nodes):
+        get = n.get if hasattr(n, "get") else (lambda k, d=None: d)
+        out.append(Style(parse_style({"color": get("color", PALETTE[(first_index + i) % len(PALETTE)])}, first_index + i).color, 0.0))
+    return out
+
+
+def mesh_wanted(cfg, sim_cfg) -> bool:
+    """--draw_mesh_colliders on the command line or `sim.draw_mesh_colliders: true` in the config (it implies draw_colliders)"""
+    return bool(cfg.get("draw_mesh_colliders", False) or (sim_cfg is not None and sim_cfg.get("draw_mesh_colliders", False)))
 
 
 def wanted(cfg, sim_cfg) -> bool:
@@ -142,6 +166,46 @@ def front_opacity(cam, colliders: Sequence, means3D: Tensor, opacity: Tensor, to
     return (out, hid) if want_hidden else out
 
 
+def cast_field(cam, fields: Sequence, styles: Sequence[Style], t: Tensor, shade: Tensor, hit: Tensor, hit_base: int,
+               to_render=IDENTITY):
+    """The field pass behind `cast`: the pixel rays' nearest hits of the field colliders' drawn solids merged into t, shade, hit
+    (what `cast` returned; a field hit replaces a pixel only where its t is strictly smaller; hit becomes hit_base + index).
+    GPU tensors are updated in place by k_field_cast and returned; CPU tensors go through the fp64 definition (new fp32 tensors)."""
+    if len(fields) != len(styles):
+        raise ValueError(f"styles: {len(styles)} for {len(fields)} field colliders")
+    if not t.is_cuda:
+        t2, shade2, hit2 = XM.cast_field(cam, fields, styles, to_render, t, shade, hit, hit_base)
+        return t2.float(), shade2.float(), hit2
+    H, W = int(cam.image_height), int(cam.image_width)
+    for x, shape, dt in ((t, (H, W), torch.float32), (shade, (3, H, W), torch.float32), (hit, (H, W), torch.int32)):
+        if tuple(x.shape) != shape or x.dtype != dt or not x.is_contiguous():
+            raise ValueError(f"cast_field: a contiguous {dt} tensor of shape {shape} expected, got {x.dtype} {tuple(x.shape)}")
+    inv = _vec(X.inverse_projection(cam).reshape(16), C.c_double)
+    L.check(L.lib().nm_collider_cast_field(C.byref(_cfg(cam)), inv, _vec(to_render[0]), _vec(to_render[1]), len(fields), pack_fields(fields),
+                                           _styles(styles), int(hit_base), L.ptr(t), L.ptr(shade), L.ptr(hit), L.stream_ptr(t.device)),
+            "nm_collider_cast_field")
+    return t, shade, hit
+
+
+def front_opacity_field(cam, fields: Sequence, means3D: Tensor, opacity_front: Tensor, to_render=IDENTITY, hidden: Optional[Tensor] = None):
+    """The field pass behind `front_opacity`: opacity_front (K,1) with the entries of the Gaussians the field colliders hide zeroed
+    too [and `hidden` (K,) uint8 with their flags set].  GPU tensors (contiguous fp32 / uint8) are updated in place by k_field_hide."""
+    if not means3D.is_cuda:
+        more = XM.hidden_field(cam.camera_center, fields, means3D, to_render)
+        out = torch.where(more[:, None], torch.zeros_like(opacity_front), opacity_front)
+        return out if hidden is None else (out, (more | hidden.bool()).to(torch.uint8))
+    m = means3D.detach().float().contiguous()
+    K = m.shape[0]
+    if opacity_front.numel() != K or opacity_front.dtype != torch.float32 or not opacity_front.is_contiguous():
+        raise ValueError(f"opacity_front: {K} contiguous fp32 values expected")
+    if hidden is not None and (hidden.numel() != K or hidden.dtype != torch.uint8 or not hidden.is_contiguous()):
+        raise ValueError(f"hidden: {K} contiguous uint8 values expected")
+    campos = _vec(cam.camera_center.detach().float().cpu().reshape(3))
+    L.check(L.lib().nm_collider_hide_field(campos, _vec(to_render[0]), _vec(to_render[1]), len(fields), pack_fields(fields), K, L.ptr(m),
+                                           L.ptr(opacity_front), L.ptr(hidden), L.stream_ptr(m.device)), "nm_collider_hide_field")
+    return opacity_front if hidden is None else (opacity_front, hidden)
+
+
 def compose(cam, img_all: Tensor, rgb_front: Tensor, a_front: Tensor, shade: Tensor, hit: Tensor,
             tile_rows: Optional[Tuple[int, int]] = None, out: Optional[Tensor] = None) -> Tensor:
     """rgb_front + (1 - a_front) shade where hit >= 0, img_all elsewhere.  a_front: (3,H,W) (channel 0 is used) or (H,W).
@@ -169,15 +233,20 @@ _BG0 = {}      # device -> the black background of the front passes (one tensor:
 
 
 def draw(img_all: Tensor, cam, colliders: Sequence, styles: Sequence[Style], to_render,
-         render_front: Callable[[Tensor, Tensor], Tuple[Tensor, Tensor]], means3D: Tensor, opacity: Tensor) -> Tensor:
+         render_front: Callable[[Tensor, Tensor], Tuple[Tensor, Tensor]], means3D: Tensor, opacity: Tensor,
+         fields: Sequence = (), field_styles: Sequence[Style] = ()) -> Tensor:
     """One drawn view.  img_all: the view as rendered today; means3D (K,3), opacity (K,1): what it was rendered from.
     render_front(opacity_front, bg0) -> (rgb_front, a_front): the frame's colours and a colors_precomp = 1 pass, both with the
-    given opacities over the black background bg0 (front_renderer builds it from diff_rasterization).  Without colliders the
-    image is returned as it is."""
-    if not colliders:
+    given opacities over the black background bg0 (front_renderer builds it from diff_rasterization).  fields, field_styles:
+    the model's field (mesh) colliders and parse_mesh_styles of their entries; their two passes run behind the analytic ones.
+    Without colliders the image is returned as it is."""
+    if not colliders and not fields:
         return img_all
-    _, shade, hit = cast(cam, colliders, styles, to_render, device=img_all.device)
+    t, shade, hit = cast(cam, colliders, styles, to_render, device=img_all.device)
     op_front = front_opacity(cam, colliders, means3D, opacity, to_render)
+    if fields:
+        _, shade, hit = cast_field(cam, fields, field_styles, t, shade, hit, len(colliders), to_render)
+        op_front = front_opacity_field(cam, fields, means3D, op_front, to_render)
     bg0 = _BG0.get(img_all.device)
     if bg0 is None:
         bg0 = _BG0[img_all.device] = torch.zeros(3, dtype=torch.float32, device=img_all.device)

@@ -1,7 +1,7 @@
 // Field colliders of the per-operator MPM path: obstacles whose shape is a signed distance field on a regular lattice (a mesh:
 // neuma_amd/mesh_sdf.py).  No reference counterpart; definition: include/neuma_hip.h "Field colliders", fp64 yardstick:
-// neuma_amd/extras/colliders.py apply_field_collider.  field_normal is the geometry (trilinear phi and its analytic gradient in
-// the cell that holds the node), field_apply one collider's response at one node, field_adjoint the transpose of its Jacobian
+// neuma_amd/extras/colliders.py apply_field_collider.  field_cell is the trilinear sample, field_normal the geometry (phi and
+// its analytic gradient in the cell that holds the node), field_apply one collider's response at one node, field_adjoint the transpose of its Jacobian
 // du'/du.  The response given the normal is the sticky / slip / friction law of nm_collide.h, spelled again here: nm_collide.h
 // and the kernels built from it stay as they are.  The kernels that sweep the active blocks (k_grid_collide_field,
 // k_grid_collide_field_bwd) and their launch sites are in nm_mpm.hip; the set travels by value in the kernel arguments, and
@@ -13,6 +13,34 @@ struct FieldColliderSet {
   int n;
   nm_field_collider c[NM_MAX_FIELD_COLLIDERS];
 };
+
+// The trilinear interpolant of one lattice cell, in two steps so that a caller that only needs the sign pays for no more: the
+// eight corner values at f (strides sx, sy, 1) and the fractions t give phi and g_x (field_cell); the same intermediate values
+// give g_y and g_z (field_cell_grad_yz).  The gradient is that of the interpolant in t: per cell, not per unit length.
+// Shared by field_normal (the grid) and the sphere trace of nm_field_ray.h (the renders).
+struct FieldCell {
+  float d00, d01, d10, d11;      // the z differences, whose bilinear interpolant is d phi / d t_z
+  float e0, e1;                  // y differences at x0, x1
+  float gx, phi;
+};
+__device__ __forceinline__ FieldCell field_cell(const float* __restrict__ f, size_t sx, size_t sy, const float t[3]) {
+  const float f000 = f[0], f001 = f[1], f010 = f[sy], f011 = f[sy + 1];
+  const float f100 = f[sx], f101 = f[sx + 1], f110 = f[sx + sy], f111 = f[sx + sy + 1];
+  FieldCell k;
+  // along z, then y, then x
+  k.d00 = f001 - f000; k.d01 = f011 - f010; k.d10 = f101 - f100; k.d11 = f111 - f110;
+  const float a00 = f000 + t[2] * k.d00, a01 = f010 + t[2] * k.d01, a10 = f100 + t[2] * k.d10, a11 = f110 + t[2] * k.d11;
+  k.e0 = a01 - a00; k.e1 = a11 - a10;
+  const float b0 = a00 + t[1] * k.e0, b1 = a10 + t[1] * k.e1;
+  k.gx = b1 - b0;
+  k.phi = b0 + t[0] * k.gx;
+  return k;
+}
+__device__ __forceinline__ void field_cell_grad_yz(const FieldCell& k, const float t[3], float& gy, float& gz) {
+  gy = k.e0 + t[0] * (k.e1 - k.e0);
+  const float z0 = k.d00 + t[1] * (k.d01 - k.d00), z1 = k.d10 + t[1] * (k.d11 - k.d10);
+  gz = z0 + t[0] * (z1 - z0);
+}
 
 // is the node at p inside the field collider (phi < 0)?  n: the outward unit normal there (only defined when inside).
 // A node off the lattice - or a NaN coordinate - is outside.  The cell index is clamped to dims - 2, so the eight corners read
@@ -29,20 +57,11 @@ __device__ __forceinline__ bool field_normal(const nm_field_collider& c, const f
     t[a] = q - f;
   }
   const size_t sy = (size_t)c.dims[2], sx = (size_t)c.dims[1] * sy;
-  const float* __restrict__ f = c.phi + ((size_t)i[0] * sx + (size_t)i[1] * sy + (size_t)i[2]);
-  const float f000 = f[0], f001 = f[1], f010 = f[sy], f011 = f[sy + 1];
-  const float f100 = f[sx], f101 = f[sx + 1], f110 = f[sx + sy], f111 = f[sx + sy + 1];
-  // along z, then y, then x; d__ are the z differences, whose bilinear interpolant is d phi / d t_z
-  const float d00 = f001 - f000, d01 = f011 - f010, d10 = f101 - f100, d11 = f111 - f110;
-  const float a00 = f000 + t[2] * d00, a01 = f010 + t[2] * d01, a10 = f100 + t[2] * d10, a11 = f110 + t[2] * d11;
-  const float e0 = a01 - a00, e1 = a11 - a10;      // y differences at x0, x1
-  const float b0 = a00 + t[1] * e0, b1 = a10 + t[1] * e1;
-  const float gx = b1 - b0;
-  const float phi = b0 + t[0] * gx;
-  if (!(phi < 0.f)) return false;
-  const float gy = e0 + t[0] * (e1 - e0);
-  const float z0 = d00 + t[1] * (d01 - d00), z1 = d10 + t[1] * (d11 - d10);
-  const float gz = z0 + t[0] * (z1 - z0);
+  const FieldCell k = field_cell(c.phi + ((size_t)i[0] * sx + (size_t)i[1] * sy + (size_t)i[2]), sx, sy, t);
+  if (!(k.phi < 0.f)) return false;
+  const float gx = k.gx;
+  float gy, gz;
+  field_cell_grad_yz(k, t, gy, gz);
   const float l2 = gx * gx + gy * gy + gz * gz;
   if (l2 > 0.f) {
     const float inv = 1.f / sqrtf(l2);

@@ -16,7 +16,8 @@ rotated coefficients when rotate_sh is on), also with an empty -dv list; `python
 any camera.
 
 `--draw_colliders` (or `sim.draw_colliders: true`; no reference counterpart): the colliders of `sim.colliders` are drawn into every
-frame, under the inverse of the ori_bounds -> sim_bounds alignment (neuma_amd/collider_draw.py)."""
+frame, under the inverse of the ori_bounds -> sim_bounds alignment (neuma_amd/collider_draw.py).  `--draw_mesh_colliders` (or
+`sim.draw_mesh_colliders: true`) implies it and draws the mesh colliders too."""
 import argparse
 import random
 from pathlib import Path
@@ -56,6 +57,8 @@ def parse_args(argv=None):
     p.add_argument("--result_root", type=str, default=RESULT)
     p.add_argument("--rotate_sh", action="store_true", help="Rotate the SH colours with the deformation (gaussian.rotate_sh).")
     p.add_argument("--draw_colliders", action="store_true", help="Draw the colliders of sim.colliders into every frame (sim.draw_colliders).")
+    p.add_argument("--draw_mesh_colliders", action="store_true",
+                   help="Draw the mesh colliders too (sim.draw_mesh_colliders); implies --draw_colliders.")
     return p.parse_args(argv)
 
 
@@ -117,16 +120,20 @@ def evaluate(cfg: Cfg, on_frame=None):
     if cfg.get("sim_dt") is not None:
         cfg.sim.dt = cfg.sim_dt
     model = MPMModelBuilder().parse_cfg(cfg.sim).finalize(device, False)
-    draw_styles = None
-    if collider_draw.wanted(cfg, cfg.sim):
-        if model.colliders:
-            draw_styles = collider_draw.parse_styles(list(cfg.sim.get("colliders"))[:len(model.colliders)])      # (mesh entries follow them)
+    draw_styles, mesh_styles = None, None
+    draw_mesh = collider_draw.mesh_wanted(cfg, cfg.sim)                      # implies draw_colliders
+    if collider_draw.wanted(cfg, cfg.sim) or draw_mesh:
+        nodes = list(cfg.sim.get("colliders") or [])
+        if draw_mesh and model.field_colliders:
+            mesh_styles = collider_draw.parse_mesh_styles(nodes[len(model.colliders):], len(model.colliders))
+        if model.colliders or mesh_styles:
+            draw_styles = collider_draw.parse_styles(nodes[:len(model.colliders)])      # (mesh entries follow them)
         else:
             print("draw_colliders: sim.colliders is empty, nothing to draw")
     if model.colliders:
         print(describe_colliders(model.colliders, drawn=draw_styles is not None))
     if model.field_colliders:
-        print(describe_field_colliders(model.field_colliders, draw_wanted=collider_draw.wanted(cfg, cfg.sim)))
+        print(describe_field_colliders(model.field_colliders, draw_wanted=collider_draw.wanted(cfg, cfg.sim), drawn=mesh_styles is not None))
     sim = MPMForwardSim(model)
     state_initializer, statics_initializer = MPMStateInitializer(model), MPMStaticsInitializer(model)
     init_data = particle_init_data(cfg, eval_steps)
@@ -149,7 +156,8 @@ def evaluate(cfg: Cfg, on_frame=None):
         cov, opa = gaussians.get_covariance(scaling_modifier=scal), gaussians.get_opacity
         front = collider_draw.front_renderer(means3D, deform_grad, cam, gaussians.active_sh_degree, cov,
                                              gaussians.get_features if shs is None else shs)
-        return collider_draw.draw(img, cam, model.colliders, draw_styles, to_render, front, means3D, opa)
+        fields = model.field_colliders if mesh_styles is not None else ()
+        return collider_draw.draw(img, cam, model.colliders, draw_styles, to_render, front, means3D, opa, fields, mesh_styles or ())
 
     for vw in views:                                                       # first frame: un-deformed kernels (render.py:292-297)
         cam = dataset.getCameras(vw, first_step)

@@ -51,7 +51,7 @@ def denormalize_points(points: torch.Tensor, sections: Sequence[int], state_init
 @torch.no_grad()
 def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: int, cameras: Sequence, background: torch.Tensor,
                      denormalize: bool = False, on_frame: Optional[Callable[[int, Dict], None]] = None,
-                     render: bool = True, export: bool = False, draw_styles=None) -> Iterator[Dict]:
+                     render: bool = True, export: bool = False, draw_styles=None, draw_mesh_styles=None) -> Iterator[Dict]:
     """Generator over frames 0..eval_steps.  Yields {'step', 'x', 'F', 'means3D', 'images': [per camera]}, and with `render`
     'shs', the coefficients the frame was rendered with: those of an object with `rotate_sh` are rotated once per frame, before
     the views, by the polar rotations of its bound deformation gradients; frame 0 (un-deformed) carries them as loaded.
@@ -59,7 +59,8 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
     3DGS parameter set (export.deformed_gaussians per object: its own `scaling` baked in, its own `rotate_sh` honoured), and from
     frame 1 'deform_grad', the bound deformation gradients (K,3,3) it was made from.
     With `draw_styles` (collider_draw.parse_styles of the model's colliders) every image has the colliders drawn in, at the centres
-    the model holds for that frame; `denormalize` then needs one alignment for all objects (ValueError otherwise)."""
+    the model holds for that frame; `denormalize` then needs one alignment for all objects (ValueError otherwise).  With
+    `draw_mesh_styles` too (collider_draw.parse_mesh_styles of the mesh entries) the model's field colliders are drawn as well."""
     device = model.device
     state_initializer = MPMStateInitializer(model)
     statics_initializer = MPMStaticsInitializer(model)
@@ -91,8 +92,9 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
     def drawn(img, cam, means3D, deform_grad, cov, opa, shs):
         if draw_styles is None:
             return img
-        return collider_draw.draw(img, cam, model.colliders, draw_styles, to_render,
-                                  collider_draw.front_renderer(means3D, deform_grad, cam, sh_deg, cov, shs), means3D, opa)
+        front = collider_draw.front_renderer(means3D, deform_grad, cam, sh_deg, cov, shs)
+        fields = model.field_colliders if draw_mesh_styles is not None else ()
+        return collider_draw.draw(img, cam, model.colliders, draw_styles, to_render, front, means3D, opa, fields, draw_mesh_styles or ())
 
     first = dict(step=0, x=x.clone(), F=F.clone(), means3D=torch.cat([g.get_xyz for g in gs], 0), images=[])
     if render:

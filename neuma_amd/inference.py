@@ -17,7 +17,8 @@ for the `experiments/configs/demo/*.yaml` schema (multiobj-bb-cc.yaml, generaliz
        `python -m neuma_amd.replay` renders the folder from any camera
 
     -> with --draw_colliders (or `sim.draw_colliders: true`; no reference counterpart) the colliders of `sim.colliders` are drawn into
-       every frame (neuma_amd/collider_draw.py); with `denormalize` the objects must then share one ori_bounds -> sim_bounds alignment
+       every frame (neuma_amd/collider_draw.py), and with --draw_mesh_colliders (`sim.draw_mesh_colliders: true`; it implies the
+       former) its mesh colliders too, by a sphere trace of their distance fields; with `denormalize` the objects must then share one ori_bounds -> sim_bounds alignment
 
 The numeric work is infer.simulate_objects (the operators of SURVEY 8 f3) on the HIP kernels.  Not reproduced: packing the
 frames into an mp4 (mediapy; --skip_frames / --remove_images are accepted, the latter removes the frames) and the random
@@ -61,6 +62,8 @@ def parse_args(argv=None):
     p.add_argument("--result_root", type=str, default=RESULT)
     p.add_argument("--rotate_sh", action="store_true", help="Rotate every object's SH colours with its deformation (gaussian.rotate_sh).")
     p.add_argument("--draw_colliders", action="store_true", help="Draw the colliders of sim.colliders into every frame (sim.draw_colliders).")
+    p.add_argument("--draw_mesh_colliders", action="store_true",
+                   help="Draw the mesh colliders too (sim.draw_mesh_colliders); implies --draw_colliders.")
     return p.parse_args(argv)
 
 
@@ -172,16 +175,20 @@ def inference(cfg: Cfg, on_frame=None):
         gauss_root.mkdir(parents=True, exist_ok=True)
     eval_steps = int(cfg.eval_steps)
     model = MPMModelBuilder().parse_cfg(cfg.sim).finalize(device, False)          # the YAML's own sim.eps (no override here)
-    draw_styles = None
-    if collider_draw.wanted(cfg, cfg.sim):
-        if model.colliders:
-            draw_styles = collider_draw.parse_styles(list(cfg.sim.get("colliders"))[:len(model.colliders)])      # (mesh entries follow them)
+    draw_styles, mesh_styles = None, None
+    draw_mesh = collider_draw.mesh_wanted(cfg, cfg.sim)                      # implies draw_colliders
+    if collider_draw.wanted(cfg, cfg.sim) or draw_mesh:
+        nodes = list(cfg.sim.get("colliders") or [])
+        if draw_mesh and model.field_colliders:
+            mesh_styles = collider_draw.parse_mesh_styles(nodes[len(model.colliders):], len(model.colliders))
+        if model.colliders or mesh_styles:
+            draw_styles = collider_draw.parse_styles(nodes[:len(model.colliders)])      # (mesh entries follow them)
         else:
             print("draw_colliders: sim.colliders is empty, nothing to draw")
     if model.colliders:
         print(describe_colliders(model.colliders, drawn=draw_styles is not None))
     if model.field_colliders:
-        print(describe_field_colliders(model.field_colliders, draw_wanted=collider_draw.wanted(cfg, cfg.sim)))
+        print(describe_field_colliders(model.field_colliders, draw_wanted=collider_draw.wanted(cfg, cfg.sim), drawn=mesh_styles is not None))
     if cfg.get("dataset_path") is not None:
         cfg.video_data.data.path = cfg.dataset_path
         print(f"Rewrite video dataset path to\n\t{cfg.dataset_path}")
@@ -196,7 +203,7 @@ def inference(cfg: Cfg, on_frame=None):
     views = [vw for vw in dataset.views if vw in debug_views]
     cameras = [dataset.getCameras(vw, first_step) for vw in views]               # the camera of the FIRST step throughout
     for frame in simulate_objects(model, objects, eval_steps, cameras, background, denormalize=bool(cfg.get("denormalize", False)),
-                                  export=gauss_root is not None, draw_styles=draw_styles):
+                                  export=gauss_root is not None, draw_styles=draw_styles, draw_mesh_styles=mesh_styles):
         step = frame["step"]
         if gauss_root is not None:
             nio.save_gaussians_ply(frame["gaussians"], gauss_root / f"{step:03d}.ply")

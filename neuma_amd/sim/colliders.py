@@ -341,9 +341,11 @@ def pack_fields(fields: Sequence):
     return arr
 
 
-def describe_fields(fields: Sequence, draw_wanted: bool = False) -> str:
-    """One line per mesh / field collider: path, triangle count, lattice, surface."""
-    lines = [f"mesh colliders: {len(fields)}" + (" (mesh colliders are not drawn in renders)" if draw_wanted else "")]
+def describe_fields(fields: Sequence, draw_wanted: bool = False, drawn: bool = False) -> str:
+    """One line per mesh / field collider: path, triangle count, lattice, surface.  drawn: the run draws them (draw_mesh_colliders);
+    draw_wanted: it draws the analytic ones only."""
+    note = " (drawn in renders)" if drawn else (" (mesh colliders are not drawn in renders)" if draw_wanted else "")
+    lines = [f"mesh colliders: {len(fields)}" + note]
     for i, c in enumerate(fields):
         src = c if isinstance(c, MeshCollider) else c.source
         what = f"mesh path={src.path} triangles={len(src.tris)}" if src is not None else "field"
