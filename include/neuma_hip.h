@@ -962,6 +962,59 @@ size_t nm_classical_bwd_workspace(int32_t n);
 int nm_classical_bwd(int32_t n, int32_t law, int32_t mode, const float* scalars, const float* F, const float* grad_out,
                      float* grad_F, float* grad_scalars, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ field paint (no reference counterpart) */
+
+/* Colouring a roll-out by a per-particle quantity (kernels: csrc/nm_paint.hip, per-particle body: csrc/nm_particle_field.h; the
+ * same definitions in torch fp64: neuma_amd/extras/field_paint.py, which is also the CPU path).  Four steps:
+ *
+ * 1. Per-particle quantity q from x, v (n, 3), F, the Kirchhoff stress tau = elasticity(F) (n, 3, 3 row-major) and the initial
+ *    position x0 (n, 3); J = det F: */
+#define NM_FIELD_SPEED 0        /* |v| */
+#define NM_FIELD_DISPLACEMENT 1 /* |x - x0| */
+#define NM_FIELD_VOLUME 2       /* J */
+#define NM_FIELD_STRAIN 3       /* Hencky equivalent strain: e_i = log(max(|s_i|, 1e-20)), s = nm_svd3(F), m = mean(e),
+                                   q = sqrt(2/3 sum_i (e_i - m)^2) */
+#define NM_FIELD_PRESSURE 4     /* -tr(tau) / (3 J); NaN where J <= 0 */
+#define NM_FIELD_VON_MISES 5    /* sigma = (tau + tau^T) / (2 J), d = sigma - tr(sigma) / 3 I, q = sqrt(3/2 sum_ab d_ab^2);
+                                   NaN where J <= 0 */
+#define NM_FIELD_COUNT 6
+/*    A NaN or Inf in an array the quantity reads gives a non-finite q.  Non-finite means "no data" in every later step.
+ *
+ * 2. Per-Gaussian value over the binding CSR (rowptr (K + 1), col, val: tune.Bindings):
+ *      g_k = (sum_j val_kj q[col_kj]) / (sum_j val_kj), over the row in CSR order, both sums in fp32;
+ *    NaN for an empty row, a weight sum of 0, a bound q that is non-finite, and a column index outside [0, n) (never read).
+ *
+ * 3. Range [lo, hi], hi > lo: the caller's, or the minimum and maximum over the finite g_k.  When that gives hi <= lo the range
+ *    is [lo, lo + 1], and [0, 1] when there is no finite value.
+ *
+ * 4. Colour: t = clamp((g - lo) / (hi - lo), 0, 1); a colour map is n_knots rgb knots c_0 .. c_{n-1} at equal spacing,
+ *    2 <= n_knots <= NM_PAINT_MAX_KNOTS:  i = min(floor(t (n - 1)), n - 2),  u = t (n - 1) - i,  rgb = c_i + u (c_{i+1} - c_i).
+ *    A non-finite g takes the no-data colour.  The output is the SH DC coefficient (rgb - 1/2) / C0, C0 = 0.28209479177387814
+ *    (the rasterizer's), so a Gaussian rendered at sh_degree 0 shows exactly rgb. */
+#define NM_PAINT_MAX_KNOTS 8
+
+/* Step 1, one particle per lane; q_out (n) fp32 on the DEVICE.  Arrays the quantity does not read may be NULL (speed: v;
+ * displacement: x, x0; volume, strain: F; pressure, von_mises: F, stress); one it reads may not (-1, the message names it), nor
+ * may q_out.  n == 0 is a no-op; n < 0 or an unknown quantity -> -1 before any device work. */
+int nm_particle_field(int32_t n, int32_t quantity, const float* x, const float* v, const float* F, const float* stress,
+                      const float* x0, float* q_out, void* stream);
+/* Step 3 on the device: the minimum and maximum of the finite values of g (k, fp32) by one fixed-order reduction (no float
+ * atomics, no host read-back; both are exact, so two calls give identical bits).  range_inout: 2 DEVICE floats {lo, hi}.
+ * mode 0 writes the frame's range with the widening rule of step 3.  mode 1 folds the frame's finite minimum / maximum into the
+ * pair already there (start it at {+inf, -inf}; nothing is widened): the overall range of a sequence.  k == 0 counts as "no
+ * finite value".  workspace: nm_field_range_workspace(k) bytes of device scratch (0 for k < 0). */
+size_t nm_field_range_workspace(int32_t k);
+int nm_field_range(int32_t k, const float* g, float* range_inout, int32_t mode, void* workspace, size_t workspace_bytes,
+                   void* stream);
+/* Steps 2 and 4, one Gaussian per lane: q (n) and range_dev (2 floats {lo, hi}) on the DEVICE - a range found by nm_field_range
+ * costs no synchronisation; knots (3 n_knots floats) and nodata_rgb (3 floats) on the HOST.  g_out (k) and dc_out (k, 3) fp32
+ * on the DEVICE; either may be NULL (not written; range_dev and the map are then not needed for a call without dc_out), not
+ * both.  rowptr == NULL paints q itself: g = q, which needs k == n (the particle-colour export).  A range with hi <= lo or a
+ * non-finite bound paints everything in the no-data colour. */
+int nm_field_paint(int32_t k, int32_t n, const int32_t* rowptr, const int32_t* col, const float* val, const float* q,
+                   const float* range_dev, int32_t n_knots, const float* knots, const float* nodata_rgb, float* g_out,
+                   float* dc_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,10 @@ SIGNATURES = {
     "nm_gaussian_activate": (C.c_int, [_I32, _P, _P, _P, _F, _P, _P, _P]),
     "nm_gaussian_activate_backward": (C.c_int, [_I32, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P]),
     "nm_gaussian_deform": (C.c_int, [_I32, _P, _P, _P, _F, _P, _P, _P]),
+    "nm_particle_field": (C.c_int, [_I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "nm_field_range_workspace": (_SZ, [_I32]),
+    "nm_field_range": (C.c_int, [_I32, _P, _P, _I32, _P, _SZ, _P]),
+    "nm_field_paint": (C.c_int, [_I32, _I32, _P, _P, _P, _P, _P, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P]),
     "nm_sh_rotate": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P]),
     "nm_sh_rotate_polar": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "nm_sh_rotate_bwd_workspace": (_SZ, [_I32]),

@@ -17,7 +17,15 @@ any camera.
 
 `--draw_colliders` (or `sim.draw_colliders: true`; no reference counterpart): the colliders of `sim.colliders` are drawn into every
 frame, under the inverse of the ori_bounds -> sim_bounds alignment (neuma_amd/collider_draw.py).  `--draw_mesh_colliders` (or
-`sim.draw_mesh_colliders: true`) implies it and draws the mesh colliders too."""
+`sim.draw_mesh_colliders: true`) implies it and draws the mesh colliders too.
+
+`--color_by QUANTITY [--color_range LO HI] [--colormap NAME]` (or `gaussian.color_by` / `color_range` / `colormap`; no reference
+counterpart): every frame, the first included, is rendered a second time per view with each Gaussian coloured by the mean of
+speed, displacement, volume, strain, pressure or von_mises over its bound particles (neuma_amd/field_paint.py) ->
+images_<video_name>_<quantity>/; colliders are drawn in as in the ordinary frames.  Without --color_range every frame is scaled by
+its own range and the sequence's overall range is printed at the end.  With --save_gaussians NAME the painted frames also go to
+gaussians_NAME_<quantity>/ (degree-0 files: `python -m neuma_amd.replay ... --sh_degree 0`), and with --save_particles the particle
+files gain a fourth float property named after the quantity."""
 import argparse
 import random
 from pathlib import Path
@@ -25,7 +33,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import collider_draw, io as nio
+from . import collider_draw, field_paint, io as nio
 from .config import Cfg, load_config
 from .export import save_frame
 from .finetune import particle_init_data, setup
@@ -59,6 +67,11 @@ def parse_args(argv=None):
     p.add_argument("--draw_colliders", action="store_true", help="Draw the colliders of sim.colliders into every frame (sim.draw_colliders).")
     p.add_argument("--draw_mesh_colliders", action="store_true",
                    help="Draw the mesh colliders too (sim.draw_mesh_colliders); implies --draw_colliders.")
+    p.add_argument("--color_by", type=str, default=None, choices=field_paint.QUANTITIES,
+                   help="Render every frame a second time, coloured by this particle quantity (gaussian.color_by).")
+    p.add_argument("--color_range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="The value range of the colour map (gaussian.color_range); default: every frame's own range.")
+    p.add_argument("--colormap", type=str, default=None, choices=sorted(field_paint.COLORMAPS), help="gaussian.colormap")
     return p.parse_args(argv)
 
 
@@ -94,6 +107,15 @@ def evaluate(cfg: Cfg, on_frame=None):
     if cfg.get("save_gaussians") is not None:
         gauss_root = Path(cfg.get("result_root", RESULT)) / cfg.name / f"gaussians_{cfg.save_gaussians}"
         gauss_root.mkdir(parents=True, exist_ok=True)
+    painter = field_paint.painter_from_cfg(cfg, cfg.get("gaussian"))
+    paint_root, paint_gauss_root = None, None
+    if painter is not None:
+        paint_root = Path(cfg.get("result_root", RESULT)) / cfg.name / f"images_{cfg.video_name}_{painter.quantity}"
+        paint_root.mkdir(exist_ok=True, parents=True)
+        if gauss_root is not None:
+            paint_gauss_root = gauss_root.with_name(f"{gauss_root.name}_{painter.quantity}")
+            paint_gauss_root.mkdir(parents=True, exist_ok=True)
+        print(painter.describe())
     cfg.video_data.data.init_frame = cfg.get("init_frame")               # NOTE: manually setting (render.py:186-188)
     if cfg.get("debug_views"):
         cfg.video_data.data.used_views = list(cfg.debug_views)
@@ -149,22 +171,36 @@ def evaluate(cfg: Cfg, on_frame=None):
     rotate_sh = bool(cfg.get("rotate_sh", False) or cfg.gaussian.get("rotate_sh", False)) and gaussians.active_sh_degree > 0
     to_render = collider_draw.map_from_alignment(init_data.size, init_data.center)      # renders are de-normalised (below)
 
-    def drawn(img, cam, means3D, deform_grad, shs):
+    def drawn(img, cam, means3D, deform_grad, shs, sh_degree=None):
         """the view with the colliders drawn in, at the centres the model holds now (collider_draw.draw)"""
         if draw_styles is None:
             return img
         cov, opa = gaussians.get_covariance(scaling_modifier=scal), gaussians.get_opacity
-        front = collider_draw.front_renderer(means3D, deform_grad, cam, gaussians.active_sh_degree, cov,
+        front = collider_draw.front_renderer(means3D, deform_grad, cam, gaussians.active_sh_degree if sh_degree is None else sh_degree, cov,
                                              gaussians.get_features if shs is None else shs)
         fields = model.field_colliders if mesh_styles is not None else ()
         return collider_draw.draw(img, cam, model.colliders, draw_styles, to_render, front, means3D, opa, fields, mesh_styles or ())
+
+    def painted(step, shs, means3D, deform_grad, exported):
+        """the frame once more with the painted coefficients `shs` (painter.frame): the images and the painted Gaussian file"""
+        cov, opa = gaussians.get_covariance(scaling_modifier=scal), gaussians.get_opacity
+        for vw in views:
+            cam = dataset.getCameras(vw, first_step)
+            img = diff_rasterization(means3D, deform_grad, None, cam, background, 0, cov, opa, shs)
+            save_image(drawn(img, cam, means3D, deform_grad, shs, 0), paint_root / f"{vw}_{step:03d}.png")
+        if paint_gauss_root is not None:
+            nio.save_gaussians_ply(field_paint.painted_gaussians(exported, shs), paint_gauss_root / f"{step:03d}.ply")
 
     for vw in views:                                                       # first frame: un-deformed kernels (render.py:292-297)
         cam = dataset.getCameras(vw, first_step)
         render = diff_rasterization(gaussians.get_xyz, None, gaussians, cam, background, scaling_modifier=scal)
         save_image(drawn(render, cam, gaussians.get_xyz, None, None), image_root / f"{vw}_{first_step:03d}.png")
+    exported = None
     if gauss_root is not None:
-        save_frame(gauss_root / f"{first_step:03d}.ply", gaussians, gaussians.get_xyz, scaling_modifier=scal)
+        exported = save_frame(gauss_root / f"{first_step:03d}.ply", gaussians, gaussians.get_xyz, scaling_modifier=scal)
+    if painter is not None:                                                # frame 0: F = I, v = v0, the stress of I
+        eye = torch.eye(3, dtype=torch.float32, device=device).expand(x.shape[0], 3, 3).contiguous()
+        painted(first_step, painter.frame(x.to(device), v.to(device), eye, E, bindings), gaussians.get_xyz, None, exported)
     de_x = denormalize_points_helper_func(x, init_data.size, init_data.center)
     de_x_prev, g_prev = de_x.clone().detach(), gaussians.get_xyz.clone().detach()
     for step in range(1, eval_steps + 1):
@@ -191,13 +227,22 @@ def evaluate(cfg: Cfg, on_frame=None):
                                                 gaussians.get_covariance(scaling_modifier=scal), gaussians.get_opacity, shs)
             images[vw] = drawn(images[vw], cam, means3D, deform_grad, shs)
             save_image(images[vw], image_root / f"{vw}_{first_step + step:03d}.png")
-        if state_root is not None:
+        paint_shs = painter.frame(x, v, F, E, bindings) if painter is not None else None
+        if state_root is not None and painter is None:
             nio.save_particles_ply(state_root / f"{first_step + step:03d}.ply", x.detach().cpu().numpy())
+        elif state_root is not None:
+            field_paint.save_particles_ply(state_root / f"{first_step + step:03d}.ply", x, painter.last_q, painter.quantity)
+        exported = None
         if gauss_root is not None:
-            save_frame(gauss_root / f"{first_step + step:03d}.ply", gaussians, means3D, deform_grad, shs, scal)
+            exported = save_frame(gauss_root / f"{first_step + step:03d}.ply", gaussians, means3D, deform_grad, shs, scal)
+        if painter is not None:
+            painted(first_step + step, paint_shs, means3D, deform_grad, exported)
         if on_frame is not None:
             on_frame(step, dict(x=x, F=F, means3D=means3D, deform_grad=deform_grad, images=images))
         de_x_prev, g_prev = de_x.clone().detach(), means3D.clone().detach()
+    said = painter.summary() if painter is not None else None
+    if said is not None:
+        print(said)
     return image_root
 
 

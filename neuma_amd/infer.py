@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from . import collider_draw
 from .export import concat_gaussians, deformed_gaussians
+from .field_paint import painted_gaussians
 from .material import ComposeMaterial
 from .render.transform_utils import scale_gaussians, translate_gaussians
 from .sim import MPMForwardSim, MPMStateInitializer, MPMStaticsInitializer
@@ -51,7 +52,7 @@ def denormalize_points(points: torch.Tensor, sections: Sequence[int], state_init
 @torch.no_grad()
 def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: int, cameras: Sequence, background: torch.Tensor,
                      denormalize: bool = False, on_frame: Optional[Callable[[int, Dict], None]] = None,
-                     render: bool = True, export: bool = False, draw_styles=None, draw_mesh_styles=None) -> Iterator[Dict]:
+                     render: bool = True, export: bool = False, draw_styles=None, draw_mesh_styles=None, painter=None) -> Iterator[Dict]:
     """Generator over frames 0..eval_steps.  Yields {'step', 'x', 'F', 'means3D', 'images': [per camera]}, and with `render`
     'shs', the coefficients the frame was rendered with: those of an object with `rotate_sh` are rotated once per frame, before
     the views, by the polar rotations of its bound deformation gradients; frame 0 (un-deformed) carries them as loaded.
@@ -60,7 +61,11 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
     frame 1 'deform_grad', the bound deformation gradients (K,3,3) it was made from.
     With `draw_styles` (collider_draw.parse_styles of the model's colliders) every image has the colliders drawn in, at the centres
     the model holds for that frame; `denormalize` then needs one alignment for all objects (ValueError otherwise).  With
-    `draw_mesh_styles` too (collider_draw.parse_mesh_styles of the mesh entries) the model's field colliders are drawn as well."""
+    `draw_mesh_styles` too (collider_draw.parse_mesh_styles of the mesh entries) the model's field colliders are drawn as well.
+    With `painter` (field_paint.FieldPainter) every frame also carries 'values' (N,), the painter's quantity per particle (frame 0:
+    F = I, the initial velocities, the stress of I), 'paint_shs' (K,1,3), each object's Gaussians painted through its own bindings
+    over one shared range, with `render` 'paint_images', the views once more at sh_degree 0 with those coefficients (colliders
+    drawn in alike), and with `export` 'paint_gaussians', the frame's Gaussians with the painted DC colour and no rest coefficients."""
     device = model.device
     state_initializer = MPMStateInitializer(model)
     statics_initializer = MPMStaticsInitializer(model)
@@ -89,13 +94,24 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
                              "single render space to draw the colliders in (render without denormalize, or align the objects alike)")
         to_render = maps[0]
 
-    def drawn(img, cam, means3D, deform_grad, cov, opa, shs):
+    def drawn(img, cam, means3D, deform_grad, cov, opa, shs, degree=None):
         if draw_styles is None:
             return img
-        front = collider_draw.front_renderer(means3D, deform_grad, cam, sh_deg, cov, shs)
+        front = collider_draw.front_renderer(means3D, deform_grad, cam, sh_deg if degree is None else degree, cov, shs)
         fields = model.field_colliders if draw_mesh_styles is not None else ()
         return collider_draw.draw(img, cam, model.colliders, draw_styles, to_render, front, means3D, opa, fields, draw_mesh_styles or ())
 
+    def painted(frame, v, F_now, means3D, deform_grad, cov, opa):
+        """the painter's part of a frame (see the docstring)"""
+        shs = painter.frame(frame["x"], v, F_now, elasticity, bindings, sections=sections)
+        frame["values"], frame["paint_shs"] = painter.last_q, shs
+        if render:
+            frame["paint_images"] = [drawn(diff_rasterization(means3D, deform_grad, None, cam, background, 0, cov, opa, shs), cam, means3D,
+                                           deform_grad, cov, opa, shs, 0) for cam in cameras]
+        if export:
+            frame["paint_gaussians"] = painted_gaussians(frame["gaussians"], shs)
+
+    bindings = [o.bindings for o in objects]
     first = dict(step=0, x=x.clone(), F=F.clone(), means3D=torch.cat([g.get_xyz for g in gs], 0), images=[])
     if render:
         cov = torch.cat([g.get_covariance(s) for g, s in zip(gs, scal)], 0)
@@ -107,13 +123,15 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
         first["shs"] = shs
     if export:
         first["gaussians"] = concat_gaussians([deformed_gaussians(g, g.get_xyz, scaling_modifier=s) for g, s in zip(gs, scal)])
+    if painter is not None:
+        painted(first, v, torch.eye(3, dtype=F.dtype, device=device).expand_as(F).contiguous(), first["means3D"], None,
+                cov if render else None, opa if render else None)
     if on_frame:
         on_frame(0, first)
     yield first
     de_x = denormalize_points(x, sections, state_initializer) if denormalize else x
     p_prev = [t.clone().detach() for t in torch.split(de_x, sections, dim=0)]
     k_prev = [g.get_xyz.clone().detach() for g in gs]
-    bindings = [o.bindings for o in objects]
     rotate_sh = [bool(o.rotate_sh) for o in objects] if (render or export) and any(o.rotate_sh for o in objects) else None
     for step in range(1, eval_steps + 1):
         stress = elasticity(F)
@@ -142,6 +160,8 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
             frame["gaussians"] = concat_gaussians([
                 deformed_gaussians(g, m, dg, sh if (rotate_sh is not None and rotate_sh[i]) else None, s)
                 for i, (g, m, dg, sh, s) in enumerate(zip(gs, *parts, scal))])
+        if painter is not None:
+            painted(frame, v, F, pack["means3D"], pack["deform_grad"], pack["cov3D"], pack["opacity"])
         if on_frame:
             on_frame(step, frame)
         yield frame

@@ -19,6 +19,13 @@ for the `experiments/configs/demo/*.yaml` schema (multiobj-bb-cc.yaml, generaliz
     -> with --draw_colliders (or `sim.draw_colliders: true`; no reference counterpart) the colliders of `sim.colliders` are drawn into
        every frame (neuma_amd/collider_draw.py), and with --draw_mesh_colliders (`sim.draw_mesh_colliders: true`; it implies the
        former) its mesh colliders too, by a sphere trace of their distance fields; with `denormalize` the objects must then share one ori_bounds -> sim_bounds alignment
+    -> with --color_by QUANTITY [--color_range LO HI] [--colormap NAME] (or the top-level keys `color_by`, `color_range`, `colormap`; no
+       reference counterpart) every frame is rendered a second time per view, each Gaussian coloured by the mean of speed, displacement,
+       volume, strain, pressure or von_mises over its bound particles (neuma_amd/field_paint.py; every object through its own bindings,
+       one range for the scene) -> images_<video_name>_<quantity>/; with --save_gaussians NAME also gaussians_NAME_<quantity>/ (degree-0
+       files for `python -m neuma_amd.replay ... --sh_degree 0`), and with --save_particles the particle files gain a fourth float
+       property named after the quantity.  Without --color_range every frame is scaled by its own range and the overall range is
+       printed at the end
 
 The numeric work is infer.simulate_objects (the operators of SURVEY 8 f3) on the HIP kernels.  Not reproduced: packing the
 frames into an mp4 (mediapy; --skip_frames / --remove_images are accepted, the latter removes the frames) and the random
@@ -34,7 +41,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import collider_draw, io as nio
+from . import collider_draw, field_paint, io as nio
 from .config import Cfg, load_config
 from .dataset import CameraDataset
 from .evaluate import save_image
@@ -64,6 +71,11 @@ def parse_args(argv=None):
     p.add_argument("--draw_colliders", action="store_true", help="Draw the colliders of sim.colliders into every frame (sim.draw_colliders).")
     p.add_argument("--draw_mesh_colliders", action="store_true",
                    help="Draw the mesh colliders too (sim.draw_mesh_colliders); implies --draw_colliders.")
+    p.add_argument("--color_by", type=str, default=None, choices=field_paint.QUANTITIES,
+                   help="Render every frame a second time, coloured by this particle quantity (color_by).")
+    p.add_argument("--color_range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="The value range of the colour map (color_range); default: every frame's own range.")
+    p.add_argument("--colormap", type=str, default=None, choices=sorted(field_paint.COLORMAPS), help="colormap")
     return p.parse_args(argv)
 
 
@@ -173,6 +185,15 @@ def inference(cfg: Cfg, on_frame=None):
     if cfg.get("save_gaussians") is not None:
         gauss_root = root / "inference" / f"gaussians_{cfg.save_gaussians}"
         gauss_root.mkdir(parents=True, exist_ok=True)
+    painter = field_paint.painter_from_cfg(cfg, cfg.get("gaussian"))
+    paint_root, paint_gauss_root = None, None
+    if painter is not None:
+        paint_root = root / "inference" / f"images_{cfg.video_name}_{painter.quantity}"
+        paint_root.mkdir(exist_ok=True, parents=True)
+        if gauss_root is not None:
+            paint_gauss_root = gauss_root.with_name(f"{gauss_root.name}_{painter.quantity}")
+            paint_gauss_root.mkdir(parents=True, exist_ok=True)
+        print(painter.describe())
     eval_steps = int(cfg.eval_steps)
     model = MPMModelBuilder().parse_cfg(cfg.sim).finalize(device, False)          # the YAML's own sim.eps (no override here)
     draw_styles, mesh_styles = None, None
@@ -203,16 +224,26 @@ def inference(cfg: Cfg, on_frame=None):
     views = [vw for vw in dataset.views if vw in debug_views]
     cameras = [dataset.getCameras(vw, first_step) for vw in views]               # the camera of the FIRST step throughout
     for frame in simulate_objects(model, objects, eval_steps, cameras, background, denormalize=bool(cfg.get("denormalize", False)),
-                                  export=gauss_root is not None, draw_styles=draw_styles, draw_mesh_styles=mesh_styles):
+                                  export=gauss_root is not None, draw_styles=draw_styles, draw_mesh_styles=mesh_styles, painter=painter):
         step = frame["step"]
         if gauss_root is not None:
             nio.save_gaussians_ply(frame["gaussians"], gauss_root / f"{step:03d}.ply")
         for vw, img in zip(views, frame["images"]):
             save_image(img, image_root / f"{vw}_{step:03d}.png")
-        if state_root is not None and step > 0:
+        if state_root is not None and step > 0 and painter is None:
             nio.save_particles_ply(state_root / f"{first_step + step:03d}.ply", frame["x"].detach().cpu().numpy())
+        elif state_root is not None and step > 0:
+            field_paint.save_particles_ply(state_root / f"{first_step + step:03d}.ply", frame["x"], frame["values"], painter.quantity)
+        if painter is not None:
+            for vw, img in zip(views, frame["paint_images"]):
+                save_image(img, paint_root / f"{vw}_{step:03d}.png")
+            if paint_gauss_root is not None:
+                nio.save_gaussians_ply(frame["paint_gaussians"], paint_gauss_root / f"{step:03d}.ply")
         if on_frame is not None:
             on_frame(step, frame)
+    said = painter.summary() if painter is not None else None
+    if said is not None:
+        print(said)
     if cfg.get("remove_images"):
         shutil.rmtree(image_root, ignore_errors=True)
     return image_root
