@@ -934,6 +934,41 @@ int nm_fill_emit(const int32_t* dims, const double* origin, double h, int32_t pe
                  const uint8_t* kind_cell, const int32_t* offsets, int64_t n_kept, float* points, uint8_t* kind_out,
                  void* stream);
 
+/* ------------------------------------------------------------------ surface meshes (no reference counterpart) */
+
+/* A closed, consistently oriented, indexed triangle mesh of the level set {f = iso} of a lattice field (neuma_amd/surface_mesh.py;
+ * extras/surface_mesh.py states the algorithm - marching tetrahedra on the Kuhn subdivision - in numpy fp64 and is the CPU path).
+ * `field` (ncells, fp32, DEVICE) in the layout of nm_fill_density: linear index (ix ny + iy) nz + iz, sample i at
+ * origin + (i + 1/2) h; `dims` 3 HOST ints, at most 2^27 cells; iso finite and > 0; a sample is inside iff f >= iso.  The
+ * lattice is extended by one ring of samples of value 0 on every side: extended dims E = dims + 2, extended sample e = i + 1,
+ * NE = E0 E1 E2, linear index (ex E1 + ey) E2 + ez.  Every extended sample owns the 7 edges to its neighbours +x, +y, +z, +x+y,
+ * +y+z, +x+z, +x+y+z (slots 0 .. 6) and the cube between itself and e + (1,1,1), cut into the six tetrahedra
+ * 000 -> e_p0 -> e_p0 + e_p1 -> 111 of the axis permutations p in lexicographic order.
+ *   nm_surface_count  mask (NE, uint8): bit s set where the ends of slot s differ in the inside test; tri_count (NE, uint8):
+ *                     triangles of the sample's cube (0 .. 12); vert_offset / tri_offset (NE, int32): exclusive prefix sums of
+ *                     popcount(mask) and tri_count in ascending extended index; info (3 DEVICE int64) = {V, T, non-finite flag}:
+ *                     the caller reads them back, refuses a non-zero flag and totals beyond int32 (the 32-bit offsets are then
+ *                     meaningless), and sizes the outputs.  One pass over the field: a workgroup stages a brick of samples with
+ *                     its +1 halo in LDS.  workspace: nm_surface_workspace(dims) bytes of device scratch (0 = invalid dims).
+ *   nm_surface_emit   the vertex of (sample, slot) lands at vert_offset[sample] + popcount(mask below slot):
+ *                     vertices (V, 3) fp32 = p_a + t (p_b - p_a), t = (iso - f_a) / (f_b - f_a) in fp32 with a the owning
+ *                     sample, the end points and the product in fp64 from `origin` (3 HOST doubles) and h, rounded to fp32
+ *                     once; normals (V, 3) = the normalised negative gradient, central differences at the two ends (0 outside
+ *                     the real lattice) interpolated with t, (0, 0, 0) for a zero gradient; vertex_attrs (V, n_attrs) from
+ *                     attrs (n_attrs <= 4, ncells; may be NULL with n_attrs = 0), a ring sample carrying the nearest real
+ *                     sample's value.  triangles (T, 3) int32 at tri_offset[cube], by tetrahedron, wound so that the normal
+ *                     points from inside to outside; zero-area triangles (a sample equal to iso) are kept, so the surface is
+ *                     closed on any finite field.  An offset outside [0, V) / [0, T) is never written through.
+ * Integer sums only: two calls give identical bytes.  Invalid dims, iso, h, origin, counts, a null pointer or a too small
+ * workspace fail before any device work; no entry synchronises with the host. */
+size_t nm_surface_workspace(const int32_t* dims);
+int nm_surface_count(const int32_t* dims, const float* field, float iso, uint8_t* mask, uint8_t* tri_count, int32_t* vert_offset,
+                     int32_t* tri_offset, int64_t* info, void* workspace, size_t workspace_bytes, void* stream);
+int nm_surface_emit(const int32_t* dims, const double* origin, double h, const float* field, float iso, int32_t n_attrs,
+                    const float* attrs, const uint8_t* mask, const uint8_t* tri_count, const int32_t* vert_offset,
+                    const int32_t* tri_offset, int64_t n_verts, int64_t n_tris, float* vertices, float* normals,
+                    float* vertex_attrs, int32_t* triangles, void* stream);
+
 /* ------------------------------------------------------------------ classical constitutive laws (material/classical.py) */
 
 /* The closed-form laws of the reference's nclaw/material/preset.py:30-282, one thread per particle.  `law`: */

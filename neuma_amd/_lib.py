@@ -196,6 +196,10 @@ SIGNATURES = {
     "nm_fill_classify_workspace": (_SZ, [C.POINTER(_I32)]),
     "nm_fill_classify": (C.c_int, [C.POINTER(_I32), _P, _F, _I32, _P, _P, _P, _P, _SZ, _P]),
     "nm_fill_emit": (C.c_int, [C.POINTER(_I32), C.POINTER(C.c_double), C.c_double, _I32, _I32, _P, _P, _I64, _P, _P, _P]),
+    "nm_surface_workspace": (_SZ, [C.POINTER(_I32)]),
+    "nm_surface_count": (C.c_int, [C.POINTER(_I32), _P, _F, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "nm_surface_emit": (C.c_int, [C.POINTER(_I32), C.POINTER(C.c_double), C.c_double, _P, _F, _I32, _P, _P, _P, _P, _P, _I64, _I64, _P,
+                                  _P, _P, _P, _P]),
     "nm_classical_fwd": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P]),
     "nm_classical_bwd_workspace": (_SZ, [_I32]),
     "nm_classical_bwd": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P]),

@@ -15,6 +15,9 @@ for the `experiments/configs/demo/*.yaml` schema (multiobj-bb-cc.yaml, generaliz
     -> <result_root>/inference/gaussians_<name>/<step:03d>.ply per frame when --save_gaussians <name> (no reference counterpart): all
        objects in one standard 3DGS file, each with its own scaling_modifier baked in (infer.simulate_objects(export=True));
        `python -m neuma_amd.replay` renders the folder from any camera
+    -> <result_root>/inference/meshes_<name>/<step:03d>.ply per frame when --save_mesh <name> [--mesh_resolution R]
+       [--mesh_density_thres T] (no reference counterpart): all objects as one closed triangle mesh with vertex colours
+       (neuma_amd/surface_mesh.py), from the same exported model, with or without --save_gaussians
 
     -> with --draw_colliders (or `sim.draw_colliders: true`; no reference counterpart) the colliders of `sim.colliders` are drawn into
        every frame (neuma_amd/collider_draw.py), and with --draw_mesh_colliders (`sim.draw_mesh_colliders: true`; it implies the
@@ -65,6 +68,11 @@ def parse_args(argv=None):
     p.add_argument("--save_particles", "-sp", type=str, default=None, help="Specify the folder name for saving simulated particles.")
     p.add_argument("--save_gaussians", type=str, default=None,
                    help="Write every frame as one 3DGS .ply of all objects into inference/gaussians_<name>/ (python -m neuma_amd.replay).")
+    p.add_argument("--save_mesh", type=str, default=None,
+                   help="Write every frame as one closed triangle mesh of all objects into inference/meshes_<name>/ (neuma_amd/surface_mesh.py).")
+    p.add_argument("--mesh_resolution", type=int, default=128, help="Lattice cells along the longest side of a frame's mesh.")
+    p.add_argument("--mesh_density_thres", type=float, default=0.5,
+                   help="Density level of the mesh surface (default not tuned on a real capture).")
     p.add_argument("--dataset_path", type=str, default=None, help="Rewrite video dataset path.")
     p.add_argument("--result_root", type=str, default=RESULT)
     p.add_argument("--rotate_sh", action="store_true", help="Rotate every object's SH colours with its deformation (gaussian.rotate_sh).")
@@ -185,6 +193,11 @@ def inference(cfg: Cfg, on_frame=None):
     if cfg.get("save_gaussians") is not None:
         gauss_root = root / "inference" / f"gaussians_{cfg.save_gaussians}"
         gauss_root.mkdir(parents=True, exist_ok=True)
+    mesh_root = None
+    if cfg.get("save_mesh") is not None:
+        from .surface_mesh import save_surface
+        mesh_root = root / "inference" / f"meshes_{cfg.save_mesh}"
+        mesh_root.mkdir(parents=True, exist_ok=True)
     painter = field_paint.painter_from_cfg(cfg, cfg.get("gaussian"))
     paint_root, paint_gauss_root = None, None
     if painter is not None:
@@ -224,10 +237,13 @@ def inference(cfg: Cfg, on_frame=None):
     views = [vw for vw in dataset.views if vw in debug_views]
     cameras = [dataset.getCameras(vw, first_step) for vw in views]               # the camera of the FIRST step throughout
     for frame in simulate_objects(model, objects, eval_steps, cameras, background, denormalize=bool(cfg.get("denormalize", False)),
-                                  export=gauss_root is not None, draw_styles=draw_styles, draw_mesh_styles=mesh_styles, painter=painter):
+                                  export=gauss_root is not None or mesh_root is not None, draw_styles=draw_styles, draw_mesh_styles=mesh_styles, painter=painter):
         step = frame["step"]
         if gauss_root is not None:
             nio.save_gaussians_ply(frame["gaussians"], gauss_root / f"{step:03d}.ply")
+        if mesh_root is not None:
+            save_surface(mesh_root / f"{step:03d}.ply", frame["gaussians"], int(cfg.get("mesh_resolution") or 128),
+                         float(cfg.get("mesh_density_thres") or 0.5))
         for vw, img in zip(views, frame["images"]):
             save_image(img, image_root / f"{vw}_{step:03d}.png")
         if state_root is not None and step > 0 and painter is None:

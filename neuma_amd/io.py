@@ -167,6 +167,68 @@ def save_particles_ply(path, points) -> None:
     write_ply_vertices(path, ["x", "y", "z"], np.asarray(points, dtype=np.float32).reshape(-1, 3))
 
 
+def _mesh_arrays(vertices, normals, colors, triangles):
+    v = np.asarray(vertices, dtype=np.float32).reshape(-1, 3)
+    n = np.zeros_like(v) if normals is None else np.asarray(normals, dtype=np.float32).reshape(-1, 3)
+    t = np.asarray(triangles, dtype=np.int32).reshape(-1, 3)
+    c = None
+    if colors is not None:
+        c = (np.clip(np.asarray(colors, dtype=np.float64).reshape(-1, 3), 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+    if len(n) != len(v) or (c is not None and len(c) != len(v)):
+        raise ValueError(f"{len(v)} vertices with {len(n)} normals" + ("" if c is None else f" and {len(c)} colours"))
+    if len(t) and (t.min() < 0 or t.max() >= len(v)):
+        raise ValueError(f"triangle index outside [0, {len(v)})")
+    return v, n, c, t
+
+
+def save_mesh_ply(path, vertices, normals, colors, triangles) -> None:
+    """A triangle mesh as binary little-endian PLY: `vertex` with float x y z nx ny nz, plus uchar red green blue when `colors`
+    ((V, 3) in [0, 1]) is given, then `face` with `list uchar int vertex_indices`.  `normals` None writes zeros.
+    `read_ply_mesh` reads it back."""
+    v, n, c, t = _mesh_arrays(vertices, normals, colors, triangles)
+    fields = [(k, "<f4") for k in ("x", "y", "z", "nx", "ny", "nz")] + ([(k, "u1") for k in ("red", "green", "blue")] if c is not None else [])
+    vert = np.zeros(len(v), dtype=np.dtype(fields))
+    for i, k in enumerate(("x", "y", "z")):
+        vert[k] = v[:, i]
+        vert["n" + k] = n[:, i]
+    if c is not None:
+        for i, k in enumerate(("red", "green", "blue")):
+            vert[k] = c[:, i]
+    face = np.zeros(len(t), dtype=np.dtype([("k", "u1"), ("idx", "<i4", (3,))]))
+    face["k"] = 3
+    face["idx"] = t
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
+    header += [f"property float {k}" for k in ("x", "y", "z", "nx", "ny", "nz")]
+    header += [f"property uchar {k}" for k in ("red", "green", "blue")] if c is not None else []
+    header += [f"element face {len(t)}", "property list uchar int vertex_indices", "end_header"]
+    Path(path).parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(vert.tobytes())
+        f.write(face.tobytes())
+
+
+def save_mesh_obj(path, vertices, normals, colors, triangles) -> None:
+    """The same mesh as Wavefront OBJ: `v x y z [r g b]`, `vn`, `f a//a b//b c//c` (1-based)."""
+    v, n, c, t = _mesh_arrays(vertices, normals, colors, triangles)
+    Path(path).parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "w") as f:
+        for i in range(len(v)):
+            rgb = "" if c is None else " %.4f %.4f %.4f" % tuple(c[i] / 255.0)
+            f.write("v %.9g %.9g %.9g%s\n" % (v[i, 0], v[i, 1], v[i, 2], rgb))
+        for i in range(len(n)):
+            f.write("vn %.6g %.6g %.6g\n" % tuple(n[i]))
+        for a, b, d in t + 1:
+            f.write(f"f {a}//{a} {b}//{b} {d}//{d}\n")
+
+
+def read_ply_mesh(path) -> Tuple[np.ndarray, np.ndarray]:
+    """(vertices (n, 3) float64, triangles (m, 3) int64) of a PLY mesh (extras.mesh_sampling.read_ply_mesh: the reader of every
+    mesh consumer here)."""
+    from .extras.mesh_sampling import read_ply_mesh as read
+    return read(path)
+
+
 def load_bindings(path, device=None):
     """bindings.pt -> (tune.Bindings with CSR + transposed CSR on `device`, n_particles (K,) float32).
     render.py:202-207 rebuilds a sparse COO tensor from the same four entries."""
