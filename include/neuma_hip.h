@@ -1050,6 +1050,33 @@ int nm_field_paint(int32_t k, int32_t n, const int32_t* rowptr, const int32_t* c
                    const float* range_dev, int32_t n_knots, const float* knots, const float* nodata_rgb, float* g_out,
                    float* dc_out, void* stream);
 
+/* ------------------------------------------------------------------ driven meshes (no reference counterpart) */
+
+/* A user's triangle mesh carried along by the particles (neuma_amd/mesh_drive.py; extras/mesh_drive.py states the definition in
+ * numpy fp64 and is the CPU path).  A vertex follows its k nearest rest particles (1 <= k <= 16) by an affine moving-least-squares
+ * fit written as fixed coefficients, so a frame is one sparse product.
+ *   nm_mesh_bind     idx (n_verts, k) int64 / d2 (n_verts, k) fp64 (DEVICE): the lists of nm_knn (query = verts, target = particles),
+ *                    ascending.  Per vertex, in fp64, every sum over j = 0 .. k-1 in that order:
+ *                      R2 = 1.21 d2_{k-1};  w_j = (1 - d2_j / R2)^2 (1 when R2 == 0);  w^_j = w_j / sum w_j
+ *                      Xbar = sum w^_j X_j (summed as X_0 + sum w^_j (X_j - X_0));  y_j = X_j - Xbar;  M = sum w^_j y_j y_j^T;  tau = tr M;  r = V0_v - Xbar
+ *                      g = (M M + (damping tau)^2 I)^-1 M r  (0 when tau == 0; L D L^T on M / tau)
+ *                      c_j = w^_j (1 + y_j . g)
+ *                    col (n_verts, k) int32 = idx, coeff = c, weight = w^ (n_verts, k) fp32, each rounded once.  The rows are a
+ *                    CSR with rowptr = k arange(n_verts + 1): position = V0 + coeff (x - X) through nm_spmm_csr or nm_bind_frame,
+ *                    vertex values through nm_field_paint over `weight`.  An index outside [0, n_particles) is never read through.
+ *                    damping finite and > 0, n_particles >= k, n_verts k < 2^31.
+ *   nm_mesh_normals  area-weighted vertex normals, fp32, no atomics, one pass.  vptr (n_verts + 1) / vcorner (3 n_tris) int32: the
+ *                    corner ids 3 t + c sorted by (vertex, corner id).  Vertex v sums, over vcorner[vptr[v] .. vptr[v + 1]) in that
+ *                    order, (p_next - p_v) x (p_prev - p_v) of the corner's triangle; a triangle with a repeated index or an index
+ *                    outside [0, n_verts) adds zero and no position is read through it; the sum is scaled by its largest
+ *                    |component| and normalised, (0, 0, 0) when it is zero or not finite.  3 n_tris < 2^31.
+ * Both: null pointers and sizes out of range fail with NM_ERR_INVALID before any device work; n_verts == 0 is a no-op; no
+ * synchronisation with the host; two calls give identical bits. */
+int nm_mesh_bind(int32_t n_verts, int32_t n_particles, int32_t k, double damping, const float* verts, const float* particles,
+                 const int64_t* idx, const double* d2, int32_t* col, float* coeff, float* weight, void* stream);
+int nm_mesh_normals(int32_t n_verts, int32_t n_tris, const float* positions, const int32_t* triangles, const int32_t* vptr,
+                    const int32_t* vcorner, float* normals_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

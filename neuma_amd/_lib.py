@@ -200,6 +200,8 @@ SIGNATURES = {
     "nm_surface_count": (C.c_int, [C.POINTER(_I32), _P, _F, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "nm_surface_emit": (C.c_int, [C.POINTER(_I32), C.POINTER(C.c_double), C.c_double, _P, _F, _I32, _P, _P, _P, _P, _P, _I64, _I64, _P,
                                   _P, _P, _P, _P]),
+    "nm_mesh_bind": (C.c_int, [_I32, _I32, _I32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "nm_mesh_normals": (C.c_int, [_I32, _I32, _P, _P, _P, _P, _P, _P]),
     "nm_classical_fwd": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P]),
     "nm_classical_bwd_workspace": (_SZ, [_I32]),
     "nm_classical_bwd": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P]),

@@ -30,7 +30,14 @@ files gain a fourth float property named after the quantity.
 `--save_mesh NAME [--mesh_resolution R] [--mesh_density_thres T]` (or `save_mesh` / `mesh_resolution` / `mesh_density_thres`; no
 reference counterpart): every frame, the first included, also goes to <result>/<name>/meshes_NAME/<frame:03d>.ply as a closed
 triangle mesh with vertex colours (neuma_amd/surface_mesh.py), built from the deformed model save_frame builds - with or without
---save_gaussians, also with an empty -dv list.  `mesh_density_thres` = 0.5 is a default nobody has tuned on a real capture yet."""
+--save_gaussians, also with an empty -dv list.  `mesh_density_thres` = 0.5 is a default nobody has tuned on a real capture yet.
+
+`--drive_mesh PATH [--drive_mesh_name NAME] [--drive_mesh_k K] [--drive_mesh_format ply|obj]` (or config keys of the same names, top
+level or under `gaussian`; no reference counterpart): the user's own mesh PATH (.obj / .ply, in the frame of kernels.ply and the
+original particles - the de-normalised frame rendered here) follows the roll-out with its vertices, faces, UVs and materials as
+they are (neuma_amd/mesh_drive.py); bound to frame 0's particles, every frame, the first included, goes to
+<result>/<name>/driven_NAME/<frame:03d>.{ply,obj} (NAME: the file stem), also with an empty -dv list; with --color_by the vertices
+carry the frame's colours."""
 import argparse
 import random
 from pathlib import Path
@@ -68,6 +75,11 @@ def parse_args(argv=None):
     p.add_argument("--mesh_resolution", type=int, default=128, help="Lattice cells along the longest side of a frame's mesh.")
     p.add_argument("--mesh_density_thres", type=float, default=0.5,
                    help="Density level of the mesh surface (default not tuned on a real capture).")
+    p.add_argument("--drive_mesh", type=str, default=None,
+                   help="Drive this triangle mesh (.obj / .ply, in the frame of kernels.ply) with the roll-out into driven_<name>/ (neuma_amd/mesh_drive.py).")
+    p.add_argument("--drive_mesh_name", type=str, default=None, help="Folder suffix of the driven frames (default: the file stem).")
+    p.add_argument("--drive_mesh_k", type=int, default=None, help="Rest particles a vertex follows, 1..16 (default 16).")
+    p.add_argument("--drive_mesh_format", type=str, default=None, choices=("ply", "obj"), help="Default ply.")
     p.add_argument("--change_base_model", "-cbm", type=str, default=None)
     p.add_argument("--dataset_path", type=str, default=None)
     p.add_argument("--transform_file", type=str, default=None)
@@ -211,6 +223,25 @@ def evaluate(cfg: Cfg, on_frame=None):
         if paint_gauss_root is not None:
             nio.save_gaussians_ply(field_paint.painted_gaussians(exported, shs), paint_gauss_root / f"{step:03d}.ply")
 
+    gsec = cfg.get("gaussian")
+    drive_key = lambda key: cfg.get(key) if cfg.get(key) is not None or gsec is None else gsec.get(key)
+    driver, driven = None, None
+    if drive_key("drive_mesh") is not None:
+        from . import mesh_drive
+        d_verts, d_tris, d_text = mesh_drive.read_mesh(drive_key("drive_mesh"))
+        d_fmt = drive_key("drive_mesh_format") or "ply"
+        drive_root = Path(cfg.get("result_root", RESULT)) / cfg.name / f"driven_{drive_key('drive_mesh_name') or Path(drive_key('drive_mesh')).stem}"
+        drive_root.mkdir(parents=True, exist_ok=True)
+
+        def driven(step, de_x_now):
+            """the user's mesh at this frame; with a painter its vertices carry the frame's colours (range and map of the Gaussians')"""
+            if painter is None:
+                pos, nrm = driver.frame(de_x_now)
+                rgb = None
+            else:
+                pos, nrm, rgb = driver.frame(de_x_now, painter.last_q, painter.frame_range, painter.colormap)
+            mesh_drive.save_frame(drive_root / f"{step:03d}.{d_fmt}", pos, nrm, rgb, driver.triangles_np, d_fmt, d_text)
+
     for vw in views:                                                       # first frame: un-deformed kernels (render.py:292-297)
         cam = dataset.getCameras(vw, first_step)
         render = diff_rasterization(gaussians.get_xyz, None, gaussians, cam, background, scaling_modifier=scal)
@@ -224,6 +255,10 @@ def evaluate(cfg: Cfg, on_frame=None):
         eye = torch.eye(3, dtype=torch.float32, device=device).expand(x.shape[0], 3, 3).contiguous()
         painted(first_step, painter.frame(x.to(device), v.to(device), eye, E, bindings), gaussians.get_xyz, None, exported)
     de_x = denormalize_points_helper_func(x, init_data.size, init_data.center)
+    if driven is not None:                                                 # bound to frame 0's particles, in the frame rendered here
+        driver = mesh_drive.MeshDriver(d_verts, d_tris, de_x, int(drive_key("drive_mesh_k") or 16), device=device)
+        print(driver.describe())
+        driven(first_step, de_x)
     de_x_prev, g_prev = de_x.clone().detach(), gaussians.get_xyz.clone().detach()
     for step in range(1, eval_steps + 1):
         stress = E(F)
@@ -261,6 +296,8 @@ def evaluate(cfg: Cfg, on_frame=None):
             meshed(first_step + step, exported, means3D, deform_grad, shs)
         if painter is not None:
             painted(first_step + step, paint_shs, means3D, deform_grad, exported)
+        if driven is not None:
+            driven(first_step + step, de_x)
         if on_frame is not None:
             on_frame(step, dict(x=x, F=F, means3D=means3D, deform_grad=deform_grad, images=images))
         de_x_prev, g_prev = de_x.clone().detach(), means3D.clone().detach()

@@ -206,6 +206,11 @@ class FieldPainter(object):
     def automatic(self) -> bool:
         return self.value_range is None
 
+    @property
+    def frame_range(self) -> Optional[Tensor]:
+        """The range the last frame was painted with: 2 device floats {lo, hi} (None before the first GPU frame)."""
+        return self._range_dev
+
     def describe(self) -> str:
         if self.automatic:
             return (f"color_by {self.quantity} ({self.colormap}): no --color_range, every frame is scaled by its own range "

@@ -39,6 +39,8 @@ class SceneObject:
     bindings: object             # tune.Bindings or a torch sparse COO tensor (K x N_obj)
     scaling: float = 1.0         # scaling_modifier of the covariances (inference.py obj_scalings)
     rotate_sh: bool = False      # `gaussian.rotate_sh`: its SH colours turn with its Gaussians' deformation (no reference counterpart)
+    name: str = ""               # the object's asset folder (`sim_data_name`)
+    drive_mesh: Optional[str] = None   # `drive_mesh`: a triangle mesh in the asset frame that follows the object (inference.py)
 
 
 def denormalize_points(points: torch.Tensor, sections: Sequence[int], state_init) -> torch.Tensor:

@@ -18,6 +18,11 @@ for the `experiments/configs/demo/*.yaml` schema (multiobj-bb-cc.yaml, generaliz
     -> <result_root>/inference/meshes_<name>/<step:03d>.ply per frame when --save_mesh <name> [--mesh_resolution R]
        [--mesh_density_thres T] (no reference counterpart): all objects as one closed triangle mesh with vertex colours
        (neuma_amd/surface_mesh.py), from the same exported model, with or without --save_gaussians
+    -> <result_root>/inference/driven_<object folder>/<step:03d>.ply per frame for every object with a `drive_mesh: PATH` key (no
+       reference counterpart): the user's own mesh (.obj / .ply, in that object's asset frame) with its vertices and faces as they
+       are, carried by the object's particles (neuma_amd/mesh_drive.py).  The mesh goes through the mapping the object's Gaussian
+       centres go through (scaled and translated into the simulation box unless `denormalize`); an object that joins late writes
+       its rest mesh until it is enabled
 
     -> with --draw_colliders (or `sim.draw_colliders: true`; no reference counterpart) the colliders of `sim.colliders` are drawn into
        every frame (neuma_amd/collider_draw.py), and with --draw_mesh_colliders (`sim.draw_mesh_colliders: true`; it implies the
@@ -53,6 +58,7 @@ from .material import InvariantFullMetaElasticity, InvariantFullMetaPlasticity, 
 from .prepare import prepare_simulation_data
 from .sim import MPMInitData, MPMModelBuilder
 from .sim.colliders import describe as describe_colliders, describe_fields as describe_field_colliders
+from .tune import denormalize_points_helper_func
 
 RESULT = "results"
 
@@ -170,7 +176,36 @@ def load_object(obj_cfg: Cfg, assets: Path, eval_steps: int, device, rotate_sh: 
     init_data.set_lin_vel(lin_vel)
     init_data.set_ang_vel(ang_vel)
     return SceneObject(init_data=init_data, elasticity=elasticity, plasticity=plasticity, gaussians=gaussians, bindings=bindings,
-                       scaling=float(gc.get("scaling_modifier", 1.0)), rotate_sh=bool(rotate_sh or gc.get("rotate_sh", False)))
+                       scaling=float(gc.get("scaling_modifier", 1.0)), rotate_sh=bool(rotate_sh or gc.get("rotate_sh", False)),
+                       name=str(obj_cfg.sim_data_name), drive_mesh=obj_cfg.get("drive_mesh"))
+
+
+class _DrivenObject(object):
+    """One object's `drive_mesh`: bound at frame 0 to the object's particles in the frame its Gaussians are rendered in."""
+
+    def __init__(self, obj: SceneObject, offset: int, denormalize: bool, root: Path, device):
+        from . import mesh_drive
+        self.md, self.obj, self.denormalize = mesh_drive, obj, denormalize
+        self.lo, self.hi = offset, offset + int(obj.init_data.num_particles)
+        verts, self.tris, _ = mesh_drive.read_mesh(obj.drive_mesh)
+        self.verts = torch.as_tensor(verts, dtype=torch.float32, device=device)
+        if not denormalize:                          # what scale_gaussians / translate_gaussians do to the centres (infer.py)
+            self.verts = self.verts * float(obj.init_data.size[0])
+            self.verts = self.verts + torch.as_tensor(obj.init_data.center, dtype=torch.float32, device=device)
+        self.root = root / "inference" / f"driven_{obj.name}"
+        self.root.mkdir(parents=True, exist_ok=True)
+        self.driver = None
+
+    def particles(self, x):
+        part = x[self.lo:self.hi]
+        return denormalize_points_helper_func(part, self.obj.init_data.size, self.obj.init_data.center) if self.denormalize else part
+
+    def write(self, step: int, x) -> None:
+        if self.driver is None:
+            self.driver = self.md.MeshDriver(self.verts, self.tris, self.particles(x), device=x.device)
+            print(f"{self.obj.name}: {self.driver.describe()}")
+        pos, nrm = self.driver.rest_frame() if step < int(self.obj.init_data.span[0]) else self.driver.frame(self.particles(x))
+        self.md.save_frame(self.root / f"{step:03d}.ply", pos, nrm, None, self.driver.triangles_np)
 
 
 @torch.no_grad()
@@ -234,6 +269,11 @@ def inference(cfg: Cfg, on_frame=None):
     first_step = dataset.steps[0]
     assets = Path(cfg.get("assets_root", "experiments/assets"))
     objects = [load_object(o, assets, eval_steps, device, rotate_sh=bool(cfg.get("rotate_sh", False))) for o in cfg.objects]
+    driven, offset = [], 0
+    for o in objects:
+        if o.drive_mesh is not None:
+            driven.append(_DrivenObject(o, offset, bool(cfg.get("denormalize", False)), root, device))
+        offset += int(o.init_data.num_particles)
     views = [vw for vw in dataset.views if vw in debug_views]
     cameras = [dataset.getCameras(vw, first_step) for vw in views]               # the camera of the FIRST step throughout
     for frame in simulate_objects(model, objects, eval_steps, cameras, background, denormalize=bool(cfg.get("denormalize", False)),
@@ -244,6 +284,8 @@ def inference(cfg: Cfg, on_frame=None):
         if mesh_root is not None:
             save_surface(mesh_root / f"{step:03d}.ply", frame["gaussians"], int(cfg.get("mesh_resolution") or 128),
                          float(cfg.get("mesh_density_thres") or 0.5))
+        for d in driven:
+            d.write(step, frame["x"])
         for vw, img in zip(views, frame["images"]):
             save_image(img, image_root / f"{vw}_{step:03d}.png")
         if state_root is not None and step > 0 and painter is None:
