@@ -37,6 +37,7 @@ extern "C" {
 #define NM_ERR_INVALID (-1)
 #define NM_ERR_HIP (-2)
 #define NM_ERR_WORKSPACE (-3)
+#define NM_ERR_LIMIT (-4) /* an iteration limit given by the caller was reached (nm_emd) */
 
 int nm_version(void);
 const char* nm_last_error(void);
@@ -860,6 +861,31 @@ int nm_knn_mean_dist2(int32_t n, const float* points, int32_t k, float* out, voi
 size_t nm_chamfer_workspace(int32_t b, int32_t n1, int32_t n2);
 int nm_chamfer(int32_t b, int32_t n1, int32_t n2, const float* p1, const float* p2, double* cd12_out, double* cd21_out,
                int64_t* idx12, int64_t* idx21, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Earth mover's distance: an exact, bitwise repeatable linear assignment between clouds a (b, n, 3) and bb (b, n, 3) of n points
+ * each (fp32, DEVICE), 1 <= n <= 8192, power 1 or 2.  No reference counterpart; neuma_amd/extras/emd.py is the numpy twin that
+ * reproduces assignment, prices and round count bit for bit.  Per item:
+ *   cost    c(i,j) = (dx*dx + dy*dy) + dz*dz in fp64 from the fp32 coordinates, in that order, no fma; power 1: its fp64 sqrt.
+ *   scale   Cmax = the same expression on the extent of the joint bounding box; frexp(Cmax) = (m, ex), k = 24 - ex,
+ *           C(i,j) = llrint(ldexp(c(i,j), k)) <= 2^24.  Cmax == 0 (all points identical): identity, emd 0, rounds 0, prices 0.
+ *   solver  forward auction in Jacobi form with eps-scaling on Cs = C (n + 1), int64: prices start at 0, eps0 = max(1, max(Cs) / 2),
+ *           eps <- max(1, eps / 4) per phase down to 1; a phase starts with nobody assigned and keeps the prices.  In a round every
+ *           unassigned person i bids from one price snapshot: v_j = -Cs(i,j) - price_j, j* the lowest j of maximal v, w1 = v_j*,
+ *           w2 = max over j != j* (w1 for n = 1), bid = price_j* + (w1 - w2) + eps; per object the highest bid wins, the lowest
+ *           person among equal bids; the previous owner becomes unassigned and the price becomes the bid.
+ *   value   emd_out[item] = mean_i c(i, idx(i)) from the unquantised fp64 costs (compensated sum, fixed order).
+ * At eps = 1 the result satisfies 1-complementary slackness on Cs, so sum C(i,idx(i)) <= opt(C) + n / (n + 1): an exact optimum
+ * of the quantised problem.  Therefore the reported value exceeds the true fp64 optimum by at most 2^-k <= Cmax * 2^-23.
+ * idx_out (b, n) int64: person -> object.  price_out (b, n) int64 or NULL: the final prices on Cs.  rounds_out (b) int64: bidding
+ * rounds.  One workgroup per item, the whole auction in one launch, every loop bounded by n or max_rounds; no n x n matrix.
+ * An item with a NaN / Inf coordinate gets emd NaN, idx -1, rounds 0 (other items are unaffected; not an error).  An item that
+ * is not finished after max_rounds rounds, or whose bid would reach 2^50 ("price overflow"), gets emd NaN, idx -1, rounds -1; the
+ * kernel finishes normally and the call returns NM_ERR_LIMIT with a message naming the first such item.  The per-item status
+ * words are read back: the call synchronises the stream once.  n outside 1..8192, power outside {1, 2}, max_rounds < 1, null
+ * pointers or a workspace smaller than nm_emd_workspace(b, n) (0 = invalid sizes): NM_ERR_INVALID before any device work. */
+size_t nm_emd_workspace(int32_t b, int32_t n);
+int nm_emd(int32_t b, int32_t n, int32_t power, int64_t max_rounds, const float* a, const float* bb, double* emd_out,
+           int64_t* idx_out, int64_t* price_out, int64_t* rounds_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ mesh sampling (particles inside a triangle mesh) */
 

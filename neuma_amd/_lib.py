@@ -186,6 +186,8 @@ SIGNATURES = {
     "nm_knn_mean_dist2": (C.c_int, [_I32, _P, _I32, _P, _P, _SZ, _P]),
     "nm_chamfer_workspace": (_SZ, [_I32, _I32, _I32]),
     "nm_chamfer": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "nm_emd_workspace": (_SZ, [_I32, _I32]),
+    "nm_emd": (C.c_int, [_I32, _I32, _I32, _I64, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "nm_mesh_inside_workspace": (_SZ, [_I32, _I32]),
     "nm_points_in_mesh": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
     "nm_mesh_distance_workspace": (_SZ, [_I32, _I64]),

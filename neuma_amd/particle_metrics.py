@@ -3,6 +3,10 @@
 cKDTree per batch item on the host; here every nearest-neighbour search is the exact grid search of one HIP entry point,
 `nm_chamfer` / `nm_nearest_neighbors` (csrc/nm_nn.hip); `k_nearest_neighbors` is the same search for 1 <= k <= 16 (`nm_knn`).
 
+`emd_native` / `earth_movers_distance` add the earth mover's distance between clouds of equal size (no reference counterpart):
+an exact, bitwise repeatable linear assignment by one HIP entry point, `nm_emd` (csrc/nm_emd.hip; the numpy twin and CPU path
+is extras/emd.py).
+
 GPU tensors only: a CPU tensor raises NeumaHipError (there is no CPU path).  Coordinates are searched on fp32 copies, so fp64
 inputs are rounded to fp32 first; the squared distances are computed in fp64 from those fp32 values, and the winner is the
 lexicographic minimum of (distance^2, index), i.e. cKDTree's fp64 choice except on exact ties.  The distances returned are
@@ -156,3 +160,69 @@ def get_nearest_neighbors_indices_batch(points_src, points_tgt, k=1):
     idx, d2 = nearest_neighbors(src, tgt)
     idx, d = idx.cpu().numpy(), torch.sqrt(d2).cpu().numpy()
     return [idx[i] for i in range(idx.shape[0])], [d[i] for i in range(d.shape[0])]
+
+
+EMD_MAX_POINTS = 8192
+
+
+def _check_emd_clouds(points1, points2):
+    _check_clouds(points1, points2)
+    if points1.shape[1] != points2.shape[1]:
+        raise ValueError(f"EMD needs clouds of equal size, got {points1.shape[1]} and {points2.shape[1]} points: subsample the "
+                         f"larger one (subsample_indices)")
+
+
+def emd_native(points1, points2, power=1, max_rounds=None, give_prices=False):
+    """One nm_emd call: (emd[B] fp64, idx[B, n] int64, rounds[B] int64[, prices[B, n] int64]) on the device, for (B, n, 3) clouds
+    of equal size 1 <= n <= 8192 and power 1 or 2.  idx[b, i] is the point of points2[b] that point i of points1[b] is assigned
+    to by the exact optimum of the quantised assignment problem (include/neuma_hip.h states it); emd[b] = mean_i c(i, idx(i))
+    from the unquantised fp64 costs of the fp32 coordinates.  The reported value exceeds the true fp64 optimum by at most
+    2^-k <= Cmax * 2^-23.  NaN / -1 / rounds 0 for an item with a NaN / Inf coordinate.  max_rounds: None = the default of
+    extras/emd.py (1667 n); an item not finished by then raises NeumaHipError naming it.  No host synchronisation besides the
+    status read-back of the call."""
+    _check_emd_clouds(points1, points2)
+    from .extras.emd import default_max_rounds
+    lib = L.lib()
+    p1 = points1.detach().float().contiguous()
+    p2 = points2.detach().float().contiguous()
+    b, n = int(p1.shape[0]), int(p1.shape[1])
+    dev = p1.device
+    emd = torch.empty(b, dtype=torch.float64, device=dev)
+    idx = torch.empty(b, n, dtype=torch.int64, device=dev)
+    rounds = torch.empty(b, dtype=torch.int64, device=dev)
+    prices = torch.empty(b, n, dtype=torch.int64, device=dev) if give_prices else None
+    ws = torch.empty(max(int(lib.nm_emd_workspace(b, n)), 1), dtype=torch.uint8, device=dev)
+    L.check(lib.nm_emd(b, n, int(power), int(default_max_rounds(n) if max_rounds is None else max_rounds), L.ptr(p1), L.ptr(p2),
+                       emd.data_ptr(), idx.data_ptr(), None if prices is None else prices.data_ptr(), rounds.data_ptr(), L.ptr(ws),
+                       ws.numel(), L.stream_ptr(dev)), "nm_emd")
+    return (emd, idx, rounds, prices) if give_prices else (emd, idx, rounds)
+
+
+def earth_movers_distance(points1, points2, power=1, give_id=False):
+    """mean_i |x_i - y_idx(i)|^power per item, shape (B,), in the input dtype, for (B, n, 3) GPU clouds of equal size n <= 8192,
+    with idx the optimal assignment of one nm_emd call (emd_native); with give_id also idx (B, n) int64.  Computed through the
+    gather, so it is differentiable in both clouds; the gradient flows through the gather, never through the (piecewise
+    constant) indices.  Unequal sizes raise ValueError: subsample the larger cloud (subsample_indices).  The value exceeds the
+    true optimum of the fp32 clouds by at most Cmax * 2^-23 plus the rounding of the input dtype."""
+    if power not in (1, 2):
+        raise ValueError(f"power must be 1 or 2, got {power}")
+    _check_emd_clouds(points1, points2)
+    if points1.shape[1] > EMD_MAX_POINTS:
+        raise ValueError(f"EMD takes at most {EMD_MAX_POINTS} points per cloud, got {points1.shape[1]}: subsample both clouds "
+                         f"(subsample_indices)")
+    emd, idx, _ = emd_native(points1, points2, power=power)
+    d2 = _gather_sq(points1, points2, idx.clamp_min(0))
+    if power == 1:          # |x - y| with the zero subgradient at coincident points (sqrt alone has slope inf there)
+        zero = d2 == 0
+        d2 = torch.where(zero, torch.zeros_like(d2), torch.where(zero, torch.ones_like(d2), d2).sqrt())
+    value = d2.mean(1)
+    value = torch.where(torch.isnan(emd), torch.full_like(value, float("nan")), value)      # a non-finite item: idx is -1 there
+    return (value, idx) if give_id else value
+
+
+def subsample_indices(N, n, seed):
+    """The sorted first n entries of numpy.random.default_rng(seed).permutation(N) as an int64 array; arange(N) when n >= N."""
+    N, n = int(N), int(n)
+    if n >= N:
+        return np.arange(N, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).permutation(N)[:n]).astype(np.int64)
