@@ -239,6 +239,33 @@ typedef struct nm_field_collider {
  * than 2^27 nodes, a null phi.  A refused call leaves the set as it was. */
 int nm_mpm_set_field_colliders(nm_mpm* h, int32_t n, const nm_field_collider* host);
 
+/* Contact report (no reference counterpart; device code: csrc/nm_contact.h; the same definition in fp64 torch:
+ * neuma_amd/extras/contact.py): the impulse the body hands to each obstacle in one substep.  With {mv, m} the grid of the
+ * substep, at every node i with m_i > 0 at p_i = (i, j, k) dx:
+ *   u^(0) = mv / (m + eps) + g dt                   (u_free)
+ *   u^(1) = BC(u^(0))                               (the box boundary condition)
+ *   u^(c+1) = collider c's response to u^(c)        (c = 1 .. R-1 in the order they are applied: analytic, then field colliders)
+ * Row r (row 0: the box walls; row r >= 1: collider r) holds NM_CONTACT_COLS doubles:
+ *   J[3]   sum_i m_i (u_i^(r) - u_i^(r+1))                    the linear impulse on the obstacle
+ *   L[3]   sum_i m_i p_i x (u_i^(r) - u_i^(r+1))              the angular impulse about the simulation origin
+ *   N      sum_i m_i (u_i^(r+1) - u_i^(r)) . n_i  over the nodes inside the collider, n_i its outward normal there: >= 0 for
+ *          slip and friction, possibly negative (adhesion) for sticky; 0 in the walls row
+ *   mass   sum m_i over the nodes with mass inside the collider (walls row: in the boundary layers, an index < bound or
+ *          >= G - bound on any axis)
+ *   nodes  the number of those nodes, as a double
+ * Momentum: sum_i m_i u_free,i - sum_r J_r is the momentum g2p hands back to the particles.  Force and torque are left to the
+ * caller: F = J / dt, torque about r0 = (L - r0 x J) / dt.  Units are simulation units: lengths of the unit cube, masses
+ * rho * vol, no conversion to world units.
+ * The velocities are evaluated in fp32 by the device functions the forward uses; differences, products and sums are fp64 in
+ * the fixed order of csrc/nm_reduce.h (no atomics: two calls on the same handle state return identical bits).
+ * Reads the grid the last nm_mpm_forward / _ex on this handle left, with the colliders the handle holds NOW: call it before
+ * moving them.  Writes only `rows` and a workspace the handle owns (allocated on first use); the grid, the lists and the counters
+ * are untouched.  Does not synchronise and reads nothing back.  With no colliders it writes the walls row alone.  NM_ERR_INVALID
+ * with a message "contact: ..." for a null handle or null rows. */
+#define NM_CONTACT_COLS 9
+/* rows: DEVICE, (1 + analytic + field colliders) x 9 doubles: walls first, then the colliders in the order they are applied */
+int nm_mpm_contact(nm_mpm* h, double* rows, void* stream);
+
 /* Drawing colliders (no reference counterpart; kernels: csrc/nm_draw.hip + csrc/nm_collide_ray.h; the same definition in fp64:
  * neuma_amd/extras/collider_draw.py; prose: DESIGN.md section 7).  Three calls in front of and behind unchanged
  * nm_raster_forward_ex renders; nothing here is differentiated.

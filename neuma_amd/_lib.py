@@ -126,6 +126,7 @@ SIGNATURES = {
     "nm_mpm_grid_export": (C.c_int, [_P, _P, _P, _P, _P]),
     "nm_mpm_set_colliders": (C.c_int, [_P, _I32, C.POINTER(nm_collider)]),
     "nm_mpm_set_field_colliders": (C.c_int, [_P, _I32, C.POINTER(nm_field_collider)]),
+    "nm_mpm_contact": (C.c_int, [_P, _P, _P]),
     "nm_collider_cast": (C.c_int, [C.POINTER(nm_raster_cfg), C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_float), _I32,
                                   C.POINTER(nm_collider), C.POINTER(nm_collider_style), _P, _P, _P, _P]),
     "nm_collider_hide": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), _I32, C.POINTER(nm_collider), _I32,

@@ -20,6 +20,8 @@
 #include "nm_grid.h"
 #include "nm_collide.h"
 #include "nm_collide_field.h"
+#include "nm_contact.h"
+#include "nm_reduce.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -54,6 +56,7 @@ struct nm_mpm {
   int fresh_rows; // g2p writes a fresh state's values into the rows of disabled particles (roll-out checkpoints, nm_grid.h)
   ColliderSet colliders;   // nm_mpm_set_colliders (host copy; travels by value in the arguments of the collider kernels)
   FieldColliderSet fields; // nm_mpm_set_field_colliders (likewise; the phi arrays stay the caller's)
+  double* contact_ws;      // nm_mpm_contact: per-workgroup partial rows, allocated on first use
 };
 int nm_mpm_num_colliders(const nm_mpm* h) { return h->colliders.n + h->fields.n; }      // analytic and field colliders alike
 void nm_mpm_set_fresh_rows(nm_mpm* h, int on) { h->fresh_rows = on; }
@@ -1435,6 +1438,37 @@ __global__ void k_grid_export(MpmK K, const float4* __restrict__ gm, const float
   if (v) { v[3 * t] = u.x; v[3 * t + 1] = u.y; v[3 * t + 2] = u.z; }
 }
 
+// Contact report (nm_contact.h; definition: include/neuma_hip.h "Contact report"): the sweep of k_grid_collide - one wave per
+// active block, one lane per node, padding nodes skipped - read-only over {mv, m}.  blockIdx.y is the row: each lane keeps the
+// nine fp64 accumulators of that one row and replays the chain up to the row's obstacle, as the collider adjoints replay it
+// (13 rows of 9 accumulators would not stay in registers).  The sums take the fixed order of nm_reduce.h: steps 1-4 here, one set
+// of partials per workgroup and row, step 5 in k_contact_sum (one workgroup per row).  No atomics: two calls give the same bits.
+__global__ void __launch_bounds__(256) k_contact_rows(const int* __restrict__ list, const int* __restrict__ count,
+                                                      const float4* __restrict__ gm, MpmK K, ColliderSet A, FieldColliderSet F,
+                                                      double* __restrict__ part) {
+  __shared__ double sh[4 * NM_CONTACT_N];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = blockIdx.y;
+  const int cnt = *count;
+  double acc[NM_CONTACT_N];
+#pragma unroll
+  for (int q = 0; q < NM_CONTACT_N; ++q) acc[q] = 0.0;
+  for (int li = blockIdx.x * 4 + wave; li < cnt; li += gridDim.x * 4) {
+    const int b = list[li];
+    int i, j, k;
+    block_coords(b, K.nb, lane, i, j, k);
+    if (!(i < K.G && j < K.G && k < K.G)) continue;      // padding nodes: velocity defined as zero, no collider acts on them
+    contact_node(K, A, F, row, i, j, k, gm[(b << 6) + lane], acc);
+  }
+  const auto tot = nm_block_reduce<4, NmSum>(acc, sh);
+  if (threadIdx.x < NM_CONTACT_N) part[((size_t)row * gridDim.x + blockIdx.x) * NM_CONTACT_N + threadIdx.x] = tot[threadIdx.x];
+}
+__global__ void __launch_bounds__(256) k_contact_sum(const double* __restrict__ part, int nb, double* __restrict__ rows) {
+  __shared__ double sh[4 * NM_CONTACT_N];
+  const auto tot = nm_block_sum_partials<4, NM_CONTACT_N>(part + (size_t)blockIdx.x * nb * NM_CONTACT_N, nb, NM_CONTACT_N, sh);
+  if (threadIdx.x < NM_CONTACT_N) rows[blockIdx.x * NM_CONTACT_N + threadIdx.x] = tot[threadIdx.x];
+}
+
 // ---------------------------------------------------------------- host API
 extern "C" int nm_mpm_create(const nm_mpm_cfg* cfg, nm_mpm** out) {
   NM_REQUIRE(cfg && out, "null cfg/out");
@@ -1487,6 +1521,7 @@ extern "C" int nm_mpm_create(const nm_mpm_cfg* cfg, nm_mpm** out) {
   h->sh_cnt = h->sh_pos = nullptr;
   h->colliders.n = 0;
   h->fields.n = 0;
+  h->contact_ws = nullptr;
   *out = h;
   return NM_OK;
 }
@@ -1501,6 +1536,7 @@ extern "C" int nm_mpm_destroy(nm_mpm* h) {
   if (h->sh_pos) hipFree(h->sh_pos);
   if (h->sh_slot) hipFree(h->sh_slot);
   if (h->sh_dil) hipFree(h->sh_dil);
+  if (h->contact_ws) hipFree(h->contact_ws);
   delete h;
   return NM_OK;
 }
@@ -2048,6 +2084,21 @@ extern "C" int nm_mpm_grid_export(nm_mpm* h, float* mv, float* m, float* v, void
   int G = h->k.G;
   NM_LAUNCH(k_grid_export, dim3(nm_div_up((int64_t)G * G * G, 256)), dim3(256), 0, (hipStream_t)stream, h->k,
                      h->gm, h->gv, mv, m, v, h->flags, h->epoch, h->colliders, h->fields);
+  NM_LAUNCH_CHECK();
+  return NM_OK;
+}
+
+extern "C" int nm_mpm_contact(nm_mpm* h, double* rows, void* stream) {
+  NM_REQUIRE(h, "contact: null handle");
+  NM_REQUIRE(rows, "contact: null rows");
+  hipStream_t s = (hipStream_t)stream;
+  const int max_rows = 1 + NM_MAX_COLLIDERS + NM_MAX_FIELD_COLLIDERS;
+  if (!h->contact_ws) NM_HIP_CHECK(hipMalloc(&h->contact_ws, (size_t)max_rows * kSweepGrid * NM_CONTACT_N * sizeof(double)));
+  const int nrows = 1 + h->colliders.n + h->fields.n;
+  NM_LAUNCH(k_contact_rows, dim3(kSweepGrid, nrows), dim3(256), 0, s, (const int*)h->list[h->cur], (const int*)(h->count + h->cur),
+                     (const float4*)h->gm, h->k, h->colliders, h->fields, h->contact_ws);
+  NM_LAUNCH_CHECK();
+  NM_LAUNCH(k_contact_sum, dim3(nrows), dim3(256), 0, s, (const double*)h->contact_ws, kSweepGrid, rows);
   NM_LAUNCH_CHECK();
   return NM_OK;
 }

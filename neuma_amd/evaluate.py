@@ -19,6 +19,10 @@ any camera.
 frame, under the inverse of the ori_bounds -> sim_bounds alignment (neuma_amd/collider_draw.py).  `--draw_mesh_colliders` (or
 `sim.draw_mesh_colliders: true`) implies it and draws the mesh colliders too.
 
+`--report_contacts` (or `sim.report_contacts: true`; no reference counterpart): the force and the torque on the box walls and on each
+collider per frame -> <result>/<name>/contacts_<video_name>.csv, and a summary at the end (neuma_amd/contact.py; simulation units).
+Images and particle files are what they are without it.
+
 `--color_by QUANTITY [--color_range LO HI] [--colormap NAME]` (or `gaussian.color_by` / `color_range` / `colormap`; no reference
 counterpart): every frame, the first included, is rendered a second time per view with each Gaussian coloured by the mean of
 speed, displacement, volume, strain, pressure or von_mises over its bound particles (neuma_amd/field_paint.py) ->
@@ -45,7 +49,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import collider_draw, field_paint, io as nio
+from . import collider_draw, contact, field_paint, io as nio
 from .config import Cfg, load_config
 from .export import deformed_gaussians, save_frame
 from .finetune import particle_init_data, setup
@@ -89,6 +93,8 @@ def parse_args(argv=None):
     p.add_argument("--draw_colliders", action="store_true", help="Draw the colliders of sim.colliders into every frame (sim.draw_colliders).")
     p.add_argument("--draw_mesh_colliders", action="store_true",
                    help="Draw the mesh colliders too (sim.draw_mesh_colliders); implies --draw_colliders.")
+    p.add_argument("--report_contacts", action="store_true",
+                   help="Write the force and torque on the walls and on each collider per frame to contacts_<video_name>.csv (sim.report_contacts).")
     p.add_argument("--color_by", type=str, default=None, choices=field_paint.QUANTITIES,
                    help="Render every frame a second time, coloured by this particle quantity (gaussian.color_by).")
     p.add_argument("--color_range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
@@ -182,6 +188,11 @@ def evaluate(cfg: Cfg, on_frame=None):
         print(describe_colliders(model.colliders, drawn=draw_styles is not None))
     if model.field_colliders:
         print(describe_field_colliders(model.field_colliders, draw_wanted=collider_draw.wanted(cfg, cfg.sim), drawn=mesh_styles is not None))
+    meter = None
+    if contact.wanted(cfg, cfg.sim):
+        meter = contact.ContactMeter(model)
+        if not (model.colliders or model.field_colliders):
+            print("report_contacts: sim.colliders is empty, reporting the box walls alone")
     sim = MPMForwardSim(model)
     state_initializer, statics_initializer = MPMStateInitializer(model), MPMStaticsInitializer(model)
     init_data = particle_init_data(cfg, eval_steps)
@@ -264,6 +275,9 @@ def evaluate(cfg: Cfg, on_frame=None):
         stress = E(F)
         state.from_torch(stress=stress)
         x, v, C, F = sim(statics, state)
+        if meter is not None:
+            meter.record()
+            meter.frame()
         model.step_colliders()                                               # moving colliders: one substep further (sim/colliders.py)
         F = P(F)
         state.from_torch(F=F)
@@ -304,6 +318,9 @@ def evaluate(cfg: Cfg, on_frame=None):
     said = painter.summary() if painter is not None else None
     if said is not None:
         print(said)
+    if meter is not None:
+        print(f"contacts: {meter.write_csv(image_root.parent / f'contacts_{cfg.video_name}.csv')}")
+        print(meter.summary())
     return image_root
 
 

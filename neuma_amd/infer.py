@@ -54,7 +54,7 @@ def denormalize_points(points: torch.Tensor, sections: Sequence[int], state_init
 @torch.no_grad()
 def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: int, cameras: Sequence, background: torch.Tensor,
                      denormalize: bool = False, on_frame: Optional[Callable[[int, Dict], None]] = None,
-                     render: bool = True, export: bool = False, draw_styles=None, draw_mesh_styles=None, painter=None) -> Iterator[Dict]:
+                     render: bool = True, export: bool = False, draw_styles=None, draw_mesh_styles=None, painter=None, meter=None) -> Iterator[Dict]:
     """Generator over frames 0..eval_steps.  Yields {'step', 'x', 'F', 'means3D', 'images': [per camera]}, and with `render`
     'shs', the coefficients the frame was rendered with: those of an object with `rotate_sh` are rotated once per frame, before
     the views, by the polar rotations of its bound deformation gradients; frame 0 (un-deformed) carries them as loaded.
@@ -67,7 +67,9 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
     With `painter` (field_paint.FieldPainter) every frame also carries 'values' (N,), the painter's quantity per particle (frame 0:
     F = I, the initial velocities, the stress of I), 'paint_shs' (K,1,3), each object's Gaussians painted through its own bindings
     over one shared range, with `render` 'paint_images', the views once more at sh_degree 0 with those coefficients (colliders
-    drawn in alike), and with `export` 'paint_gaussians', the frame's Gaussians with the painted DC colour and no rest coefficients."""
+    drawn in alike), and with `export` 'paint_gaussians', the frame's Gaussians with the painted DC colour and no rest coefficients.
+    With `meter` (contact.ContactMeter of the model) every step's contact rows are recorded before the colliders move, one frame per
+    step; nothing is read back here."""
     device = model.device
     state_initializer = MPMStateInitializer(model)
     statics_initializer = MPMStaticsInitializer(model)
@@ -139,6 +141,9 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
         stress = elasticity(F)
         state.from_torch(stress=stress)
         x, v, C, F = sim(statics, state)
+        if meter is not None:
+            meter.record()
+            meter.frame()
         model.step_colliders()                                         # moving colliders: one substep further (sim/colliders.py)
         F = plasticity(F)
         state.from_torch(F=F)

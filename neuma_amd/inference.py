@@ -34,6 +34,9 @@ for the `experiments/configs/demo/*.yaml` schema (multiobj-bb-cc.yaml, generaliz
        files for `python -m neuma_amd.replay ... --sh_degree 0`), and with --save_particles the particle files gain a fourth float
        property named after the quantity.  Without --color_range every frame is scaled by its own range and the overall range is
        printed at the end
+    -> with --report_contacts (or `sim.report_contacts: true`; no reference counterpart) the force and the torque on the box walls and
+       on each collider per frame -> <result_root>/inference/contacts_<video_name>.csv, and a summary at the end (neuma_amd/contact.py;
+       simulation units); images and particle files are what they are without it
 
 The numeric work is infer.simulate_objects (the operators of SURVEY 8 f3) on the HIP kernels.  Not reproduced: packing the
 frames into an mp4 (mediapy; --skip_frames / --remove_images are accepted, the latter removes the frames) and the random
@@ -49,7 +52,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import collider_draw, field_paint, io as nio
+from . import collider_draw, contact, field_paint, io as nio
 from .config import Cfg, load_config
 from .dataset import CameraDataset
 from .evaluate import save_image
@@ -85,6 +88,8 @@ def parse_args(argv=None):
     p.add_argument("--draw_colliders", action="store_true", help="Draw the colliders of sim.colliders into every frame (sim.draw_colliders).")
     p.add_argument("--draw_mesh_colliders", action="store_true",
                    help="Draw the mesh colliders too (sim.draw_mesh_colliders); implies --draw_colliders.")
+    p.add_argument("--report_contacts", action="store_true",
+                   help="Write the force and torque on the walls and on each collider per frame to contacts_<video_name>.csv (sim.report_contacts).")
     p.add_argument("--color_by", type=str, default=None, choices=field_paint.QUANTITIES,
                    help="Render every frame a second time, coloured by this particle quantity (color_by).")
     p.add_argument("--color_range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
@@ -258,6 +263,11 @@ def inference(cfg: Cfg, on_frame=None):
         print(describe_colliders(model.colliders, drawn=draw_styles is not None))
     if model.field_colliders:
         print(describe_field_colliders(model.field_colliders, draw_wanted=collider_draw.wanted(cfg, cfg.sim), drawn=mesh_styles is not None))
+    meter = None
+    if contact.wanted(cfg, cfg.sim):
+        meter = contact.ContactMeter(model)
+        if not (model.colliders or model.field_colliders):
+            print("report_contacts: sim.colliders is empty, reporting the box walls alone")
     if cfg.get("dataset_path") is not None:
         cfg.video_data.data.path = cfg.dataset_path
         print(f"Rewrite video dataset path to\n\t{cfg.dataset_path}")
@@ -277,7 +287,7 @@ def inference(cfg: Cfg, on_frame=None):
     views = [vw for vw in dataset.views if vw in debug_views]
     cameras = [dataset.getCameras(vw, first_step) for vw in views]               # the camera of the FIRST step throughout
     for frame in simulate_objects(model, objects, eval_steps, cameras, background, denormalize=bool(cfg.get("denormalize", False)),
-                                  export=gauss_root is not None or mesh_root is not None, draw_styles=draw_styles, draw_mesh_styles=mesh_styles, painter=painter):
+                                  export=gauss_root is not None or mesh_root is not None, draw_styles=draw_styles, draw_mesh_styles=mesh_styles, painter=painter, meter=meter):
         step = frame["step"]
         if gauss_root is not None:
             nio.save_gaussians_ply(frame["gaussians"], gauss_root / f"{step:03d}.ply")
@@ -302,6 +312,9 @@ def inference(cfg: Cfg, on_frame=None):
     said = painter.summary() if painter is not None else None
     if said is not None:
         print(said)
+    if meter is not None:
+        print(f"contacts: {meter.write_csv(root / 'inference' / f'contacts_{cfg.video_name}.csv')}")
+        print(meter.summary())
     if cfg.get("remove_images"):
         shutil.rmtree(image_root, ignore_errors=True)
     return image_root

@@ -382,6 +382,61 @@ class MPMModel(Model):
         L.check(L.lib().nm_mpm_grid_export(self.handle(), L.ptr(mv), L.ptr(m), L.ptr(v), self._stream()), "nm_mpm_grid_export")
         return mv, m, v
 
+    # -- contact report (no reference counterpart; include/neuma_hip.h "Contact report", extras/contact.py)
+    def contact_names(self):
+        """Row names of contact(): "walls", then "<index>:<kind>" per collider in the order they are applied."""
+        kinds = [type(c).__name__.lower() for c in self._colliders] + ["mesh"] * len(self._field_colliders)
+        return ["walls"] + [f"{i}:{k}" for i, k in enumerate(kinds)]
+
+    def contact(self) -> 'ContactReport':
+        """The impulse the body handed to the box walls and to each collider in the LAST substep (forward on this model), with the
+        colliders as they are now: call it before step_colliders().  Read-only and asynchronous: nothing is read back to the host."""
+        if self.exchange is not None:
+            raise L.NeumaHipError("colliders: per-operator path only (contact on a sharded model)")
+        rows = torch.empty(1 + len(self._colliders) + len(self._field_colliders), CONTACT_COLS, dtype=torch.float64, device=self.device)
+        L.check(L.lib().nm_mpm_contact(self.handle(), rows.data_ptr(), self._stream()), "nm_mpm_contact")
+        return ContactReport(rows, self.contact_names())
+
+
+CONTACT_COLS = 9      # NM_CONTACT_COLS
+
+
+@dataclass
+class ContactReport(object):
+    """One substep's (or a sum of substeps') contact rows: rows (R, 9) fp64 on the model's device - J[3], L[3] (about the simulation
+    origin), N, mass, nodes per row - and the rows' names.  Simulation units (the unit cube, rho * vol masses)."""
+    rows: Tensor
+    names: Sequence[str]
+
+    @property
+    def impulse(self) -> Tensor:
+        return self.rows[:, 0:3]
+
+    @property
+    def angular(self) -> Tensor:
+        return self.rows[:, 3:6]
+
+    @property
+    def normal(self) -> Tensor:
+        return self.rows[:, 6]
+
+    @property
+    def mass(self) -> Tensor:
+        return self.rows[:, 7]
+
+    @property
+    def nodes(self) -> Tensor:
+        return self.rows[:, 8]
+
+    def force(self, dt: float) -> Tensor:
+        """(R, 3): J / dt, dt the time the impulses were gathered in"""
+        return self.impulse / dt
+
+    def torque(self, dt: float, about=(0.0, 0.0, 0.0)) -> Tensor:
+        """(R, 3): (L - r0 x J) / dt; about: r0 (3,), or one point per row (R, 3)"""
+        r0 = torch.as_tensor(about, dtype=self.rows.dtype, device=self.rows.device).expand_as(self.impulse)
+        return (self.angular - torch.linalg.cross(r0, self.impulse)) / dt
+
 
 class MPMModelBuilder(ModelBuilder):
     """mpm.py:501-551"""
