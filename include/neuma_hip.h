@@ -847,6 +847,39 @@ int nm_image_metrics(int32_t b, int32_t c, int32_t h, int32_t w, const float* pr
                      int32_t range_per_image, double* sse_out, double* ssim_out, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* LPIPS, the third number of experiments/evaluation.py: LearnedPerceptualImagePatchSimilarity(net_type='vgg', normalize=True).
+ * For a, b (B,3,H,W) in [0,1]: x = (2 x - 1 - shift) / scale per channel (shift -0.030, -0.088, -0.188; scale 0.458, 0.448,
+ * 0.450); VGG-16's 13 convolutions (3x3, zero padding 1, bias, ReLU) with a 2x2 / stride 2 / floor max-pool after convolutions
+ * 2, 4, 7 and 10; taps after the ReLU of convolutions 2, 4, 7, 10, 13; per tap and pixel t^ = t / sqrt(1e-8 + sum_c t^2) and
+ * d = sum_c w_c (a^_c - b^_c)^2; the value of a pair is the sum over the five taps of the mean of d over the tap's pixels.
+ * Activations are CHANNELS-LAST, (N,H,W,C) fp32 contiguous, 16-byte aligned, everywhere below.  No atomics, no host
+ * synchronisation, nothing read back; two calls give identical bits, and an image's result does not depend on its batch slot.
+ *
+ * nm_conv3x3_relu  y (N,H,W,Cout) = relu(conv3x3(x (N,H,W,Cin)) + bias).  Cout % 64 == 0; Cin == 3 (plain VALU) or
+ *                  Cin % 16 == 0 (implicit GEMM on v_mfma_f32_16x16x4_f32, exact fp32: one fmaf chain over k per output, whose
+ *                  order depends on Cin alone).  weight, packed from torch's (Cout,Cin,3,3) w: Cin == 3: (Cout, 9, 3) =
+ *                  w[o][c][ky][kx] at [o][3 ky + kx][c]; otherwise (Cin/16, Cout, 9, 16) = w[o][16 j + c][ky][kx] at
+ *                  [j][o][3 ky + kx][c].  y may not alias x.
+ * nm_maxpool2      y (N,H/2,W/2,C) = 2x2 max-pool, stride 2, an odd last row / column dropped.  C % 4 == 0.
+ * nm_lpips_head    out_fp64[p] (DEVICE) = the pixel mean of d for pair p of tap_a, tap_b (n_pairs,H,W,C), C % 4 == 0, head_w C
+ *                  floats.  Norms, quotients and sums in fp64, the pixel sum in the fixed order of csrc/nm_reduce.h.
+ *                  ws: nm_lpips_head_workspace(n_pairs, h, w) bytes of device scratch.
+ * nm_lpips         the whole chain for B pairs: out_fp64[B] (DEVICE).  a, b_img: (B,3,H,W) fp32 planar, as images come.
+ *                  weights: HOST array of 26 DEVICE pointers, packed weight then bias of each convolution in order; heads:
+ *                  HOST array of 5 DEVICE pointers (64, 128, 256, 512, 512 floats).  ws: nm_lpips_workspace(b, h, w) bytes of
+ *                  device scratch, 256-byte aligned (two activation buffers of 2B x H x W x 64 floats and small change).
+ * NM_ERR_INVALID with nm_last_error text before any device work: H or W < 16 (nm_lpips; the workspace size is then 0), sizes
+ * out of range, channel counts the kernels do not take, null or misaligned pointers, a workspace that is too small. */
+int nm_conv3x3_relu(int32_t n, int32_t cin, int32_t cout, int32_t h, int32_t w, const float* x, const float* weight,
+                    const float* bias, float* y, void* stream);
+int nm_maxpool2(int32_t n, int32_t c, int32_t h, int32_t w, const float* x, float* y, void* stream);
+size_t nm_lpips_head_workspace(int32_t n_pairs, int32_t h, int32_t w);
+int nm_lpips_head(int32_t n_pairs, int32_t c, int32_t h, int32_t w, const float* tap_a, const float* tap_b, const float* head_w,
+                  double* out_fp64, void* ws, size_t ws_bytes, void* stream);
+size_t nm_lpips_workspace(int32_t b, int32_t h, int32_t w);
+int nm_lpips(int32_t b, int32_t h, int32_t w, const float* a, const float* b_img, const float* const* weights,
+             const float* const* heads, double* out_fp64, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ particle metrics (modules/tune/metrics.py) */
 
 /* Exact 1-nearest-neighbour search, batched over b pairs of clouds: query (b, n_query, 3) and target (b, n_target, 3) fp32,

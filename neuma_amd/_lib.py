@@ -179,6 +179,12 @@ SIGNATURES = {
     "nm_ssim_loss": (C.c_int, [_F, _I32, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
     "nm_image_metrics_workspace": (_SZ, [_I32, _I32, _I32, _I32]),
     "nm_image_metrics": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _SZ, _P]),
+    "nm_conv3x3_relu": (C.c_int, [_I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    "nm_maxpool2": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P]),
+    "nm_lpips_head_workspace": (_SZ, [_I32, _I32, _I32]),
+    "nm_lpips_head": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
+    "nm_lpips_workspace": (_SZ, [_I32, _I32, _I32]),
+    "nm_lpips": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "nm_nn_workspace": (_SZ, [_I32, _I32, _I32]),
     "nm_nearest_neighbors": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
     "nm_knn_workspace": (_SZ, [_I32, _I32, _I32, _I32]),

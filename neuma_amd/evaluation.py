@@ -1,13 +1,16 @@
 """Image-quality evaluation of rendered frames against the ground truth: counterpart of experiments/evaluation.py (the
 fourth stage of the NeuMA pipeline, after regist / finetune / render), reachable as
-`python -m neuma_amd.evaluation -p <pred_dir> -g <gt_dir> --view V [-s start] [-k skip] [-n num] [-d cuda]`.
+`python -m neuma_amd.evaluation -p <pred_dir> -g <gt_dir> --view V [-s start] [-k skip] [-n num] [-d cuda]
+[--lpips_vgg PATH --lpips_heads PATH]`.
 
 Frames start + i * skip (i = 0..num) are read as <dir>/e_<view>_<i:03d>.png: the prediction as RGB (alpha dropped), the ground
 truth as RGBA composited on white with the reference's truncation to uint8, both cropped to [220:580, 220:580].  PSNR and SSIM
 per frame (torchmetrics semantics, `neuma_amd.image_metrics`; one nm_image_metrics call per chunk of up to 64 frames, each frame
 with its own data range) are averaged into <pred_dir>/../<basename>_metrics.txt, and each pair is written side by side to
-results/debug/<i>.png.  LPIPS is not computed (it needs ImageNet VGG-16 weights and the LPIPS heads, which this package does
-not ship), and the pred-gt mp4 is not written (packing frames into a video is left to external tools).
+results/debug/<i>.png.  LPIPS (VGG-16, `neuma_amd.lpips`) is the third number when the user names the two public weight files it
+needs, torchvision's VGG-16 state dict (--lpips_vgg) and the LPIPS heads vgg.pth of torchmetrics / lpips (--lpips_heads): this
+package ships and fetches neither, and without the two flags LPIPS is not computed.  The pred-gt mp4 is not written (packing
+frames into a video is left to external tools).
 
 (Not to be confused with `neuma_amd/evaluate.py`, the forward roll-out + rendering of render.py's `eval`.)"""
 import argparse
@@ -29,7 +32,14 @@ def parse_args(argv=None):
     p.add_argument("--num", "-n", type=int, default=10, help="Number of images to calculate")
     p.add_argument("--device", "-d", type=str, default="cuda", help="Device to use")
     p.add_argument("--view", type=int, required=True)
-    return p.parse_args(argv)
+    p.add_argument("--lpips_vgg", type=str, default=None, help="torchvision VGG-16 state dict (.pth); with --lpips_heads: LPIPS")
+    p.add_argument("--lpips_heads", type=str, default=None, help="LPIPS heads vgg.pth of torchmetrics / lpips; with --lpips_vgg")
+    args = p.parse_args(argv)
+    if (args.lpips_vgg is None) != (args.lpips_heads is None):
+        missing = "--lpips_heads" if args.lpips_heads is None else "--lpips_vgg"
+        given = "--lpips_vgg" if args.lpips_heads is None else "--lpips_heads"
+        p.error(f"LPIPS needs both weight files: {given} was given without {missing}")
+    return args
 
 
 def frame_indices(start: int, skip: int, num: int):
@@ -87,9 +97,10 @@ def metrics_path(pred_dir: str) -> str:
     return os.path.join(pred_dir, "..", f'{pred_dir.split("/")[-1]}_metrics.txt')
 
 
-def _score(preds_u8, gts_u8, device):
-    """per-frame (psnr, ssim) lists of a chunk of (H, W, 3) uint8 crops: ToTensor (uint8 / 255 in fp32) on the device, then one
-    nm_image_metrics call with each frame's own data range.  Called as the reference does, psnr(gt, pred) / ssim(gt, pred)."""
+def _score(preds_u8, gts_u8, device, lpips=None):
+    """per-frame (psnr, ssim, lpips or None) lists of a chunk of (H, W, 3) uint8 crops: ToTensor (uint8 / 255 in fp32) on the
+    device, then one nm_image_metrics call with each frame's own data range and, given LpipsWeights, nm_lpips.  Called as the
+    reference does, psnr(gt, pred) / ssim(gt, pred) / lpips(gt, pred)."""
     import torch
     from .image_metrics import image_metrics
 
@@ -97,12 +108,18 @@ def _score(preds_u8, gts_u8, device):
         a = torch.from_numpy(np.stack(frames)).to(device)
         return a.permute(0, 3, 1, 2).float().div(255).contiguous()
 
-    psnr, ssim = image_metrics(to_tensor(gts_u8), to_tensor(preds_u8), range_per_image=True)
-    return psnr.cpu().tolist(), ssim.cpu().tolist()
+    gt, pred = to_tensor(gts_u8), to_tensor(preds_u8)
+    psnr, ssim = image_metrics(gt, pred, range_per_image=True)
+    lp = None
+    if lpips is not None:
+        from .lpips import lpips as lpips_native
+        lp = lpips_native(gt, pred, lpips).cpu().tolist()
+    return psnr.cpu().tolist(), ssim.cpu().tolist(), lp
 
 
-def calculate_synthetic_image_metrics(pred_dir, gt_dir, start, skip, num, view, device="cuda"):
-    """evaluation.py:27-97 without LPIPS and the video; returns (mean PSNR, mean SSIM)."""
+def calculate_synthetic_image_metrics(pred_dir, gt_dir, start, skip, num, view, device="cuda", lpips=None):
+    """evaluation.py:27-97 without the video; returns (mean PSNR, mean SSIM), or (mean PSNR, mean SSIM, mean LPIPS) when `lpips`
+    holds LpipsWeights (neuma_amd.lpips.load_weights, which records the two files' names for the notice)."""
     import torch
     from PIL import Image
 
@@ -110,9 +127,13 @@ def calculate_synthetic_image_metrics(pred_dir, gt_dir, start, skip, num, view, 
     idx = frame_indices(start, skip, num)
     os.makedirs(DEBUG_DIR, exist_ok=True)
     print(f"current pred_dir: {pred_dir}, skip: {skip}, from {start} to {start + num * skip}")
-    print("LPIPS is not computed (no VGG-16 / LPIPS weights are shipped) and the pred-gt mp4 is not written (no video "
-          "encoder); the metrics file holds PSNR and SSIM only")
-    psnr_all, ssim_all = [], []
+    if lpips is None:
+        print("LPIPS is not computed (no VGG-16 / LPIPS weights are shipped) and the pred-gt mp4 is not written (no video "
+              "encoder); the metrics file holds PSNR and SSIM only")
+    else:
+        vgg_file, heads_file = lpips.files or ("<weights given as tensors>",) * 2
+        print(f"LPIPS from VGG-16 weights {vgg_file} and heads {heads_file}; the pred-gt mp4 is not written (no video encoder)")
+    psnr_all, ssim_all, lpips_all = [], [], []
     for c0 in range(0, len(idx), CHUNK):
         chunk = idx[c0:c0 + CHUNK]
         names, preds, gts = [], [], []
@@ -121,23 +142,35 @@ def calculate_synthetic_image_metrics(pred_dir, gt_dir, start, skip, num, view, 
             preds.append(crop(load_pred(pred_path)))
             gts.append(crop(load_gt(gt_path)))
             names.append((os.path.basename(pred_path), os.path.basename(gt_path)))
-        psnr, ssim = _score(preds, gts, device)
-        for i, (pn, gn), p, g, pv, sv in zip(chunk, names, preds, gts, psnr, ssim):
-            print(f"pr: {pn} [{p.shape}] | gt: {gn} [{g.shape}] | PSNR: {pv:.2f} | SSIM: {sv:.2f}")
+        psnr, ssim, lp = _score(preds, gts, device, lpips)
+        for j, (i, (pn, gn), p, g, pv, sv) in enumerate(zip(chunk, names, preds, gts, psnr, ssim)):
+            tail = "" if lp is None else f" | LPIPS: {lp[j]:.2f}"
+            print(f"pr: {pn} [{p.shape}] | gt: {gn} [{g.shape}] | PSNR: {pv:.2f} | SSIM: {sv:.2f}{tail}")
             Image.fromarray(debug_pair(p, g), "RGB").save(os.path.join(DEBUG_DIR, f"{i}.png"))
         psnr_all += psnr
         ssim_all += ssim
+        lpips_all += lp or []
     psnr_avg = sum(psnr_all) / len(psnr_all)           # AverageMeter: plain mean, inf / nan propagate
     ssim_avg = sum(ssim_all) / len(ssim_all)
     with open(metrics_path(pred_dir), "w") as f:
         f.write(f"PSNR: {psnr_avg:.2f}\n")
         f.write(f"SSIM: {ssim_avg:.2f}\n")
+        if lpips is not None:
+            lpips_avg = sum(lpips_all) / len(lpips_all)
+            f.write(f"LPIPS: {lpips_avg:.4f}\n")
+    if lpips is not None:
+        return psnr_avg, ssim_avg, lpips_avg
     return psnr_avg, ssim_avg
 
 
 def main(argv=None):
     args = parse_args(argv)
-    calculate_synthetic_image_metrics(args.pred_dir, args.gt_dir, args.start, args.skip, args.num, args.view, args.device)
+    weights = None
+    if args.lpips_vgg is not None:
+        from .lpips import load_weights
+        weights = load_weights(args.lpips_vgg, args.lpips_heads, args.device)
+    calculate_synthetic_image_metrics(args.pred_dir, args.gt_dir, args.start, args.skip, args.num, args.view, args.device,
+                                      lpips=weights)
 
 
 if __name__ == "__main__":
