@@ -54,13 +54,15 @@ def denormalize_points(points: torch.Tensor, sections: Sequence[int], state_init
 @torch.no_grad()
 def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: int, cameras: Sequence, background: torch.Tensor,
                      denormalize: bool = False, on_frame: Optional[Callable[[int, Dict], None]] = None,
-                     render: bool = True, export: bool = False, draw_styles=None, draw_mesh_styles=None, painter=None, meter=None) -> Iterator[Dict]:
-    """Generator over frames 0..eval_steps.  Yields {'step', 'x', 'F', 'means3D', 'images': [per camera]}, and with `render`
-    'shs', the coefficients the frame was rendered with: those of an object with `rotate_sh` are rotated once per frame, before
-    the views, by the polar rotations of its bound deformation gradients; frame 0 (un-deformed) carries them as loaded.
+                     render: bool = True, export: bool = False, draw_styles=None, draw_mesh_styles=None, painter=None, meter=None,
+                     init_state=None) -> Iterator[Dict]:
+    """Generator over frames 0..eval_steps.  Yields {'step', 'x', 'F', 'means3D', 'images': [per camera]}, from frame 1
+    'deform_grad', the bound deformation gradients (K,3,3), and with `render` 'shs', the coefficients the frame was rendered with:
+    those of an object with `rotate_sh` are rotated once per frame, before the views, by the polar rotations of its bound
+    deformation gradients; frame 0 (un-deformed) carries them as loaded.  `init_state` = (x, v, C, F) replaces the particle state
+    the objects' init_data give (the render driver's fitted initial positions and velocities).
     With `export` every frame also carries 'gaussians': one GaussianModel of all objects in object order, the frame as a standard
-    3DGS parameter set (export.deformed_gaussians per object: its own `scaling` baked in, its own `rotate_sh` honoured), and from
-    frame 1 'deform_grad', the bound deformation gradients (K,3,3) it was made from.
+    3DGS parameter set (export.deformed_gaussians per object: its own `scaling` baked in, its own `rotate_sh` honoured).
     With `draw_styles` (collider_draw.parse_styles of the model's colliders) every image has the colliders drawn in, at the centres
     the model holds for that frame; `denormalize` then needs one alignment for all objects (ValueError otherwise).  With
     `draw_mesh_styles` too (collider_draw.parse_mesh_styles of the mesh entries) the model's field colliders are drawn as well.
@@ -78,6 +80,8 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
         statics_initializer.add_group(o.init_data)
     state, sections = state_initializer.finalize()
     statics = statics_initializer.finalize()
+    if init_state is not None:
+        state.from_torch(*init_state)
     x, v, C, F, stress = state.to_torch()
     elasticity = ComposeMaterial([o.elasticity for o in objects], sections).to(device).eval()
     plasticity = ComposeMaterial([o.plasticity for o in objects], sections).to(device).eval()
@@ -154,7 +158,7 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
         pack = preprocess_for_rasterization(obj_gaussians=gs, obj_deform_grad=dgs, obj_kernels_prev=k_prev, obj_particles_curr=p_curr,
                                             obj_particles_prev=p_prev, obj_bindings=bindings, obj_scalings=scal,
                                             obj_rotate_sh=rotate_sh)
-        frame = dict(step=step, x=x.clone(), F=F.clone(), means3D=pack["means3D"], images=[])
+        frame = dict(step=step, x=x.clone(), F=F.clone(), means3D=pack["means3D"], deform_grad=pack["deform_grad"], images=[])
         if render:
             for cam in cameras:
                 img = diff_rasterization(pack["means3D"], pack["deform_grad"], None, cam, background,
@@ -163,7 +167,6 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
             frame["shs"] = pack["shs"]
         if export:
             parts = [torch.split(pack[k], sec_gaussians, dim=0) for k in ("means3D", "deform_grad", "shs")]
-            frame["deform_grad"] = pack["deform_grad"]
             frame["gaussians"] = concat_gaussians([
                 deformed_gaussians(g, m, dg, sh if (rotate_sh is not None and rotate_sh[i]) else None, s)
                 for i, (g, m, dg, sh, s) in enumerate(zip(gs, *parts, scal))])

@@ -38,7 +38,8 @@ for the `experiments/configs/demo/*.yaml` schema (multiobj-bb-cc.yaml, generaliz
        on each collider per frame -> <result_root>/inference/contacts_<video_name>.csv, and a summary at the end (neuma_amd/contact.py;
        simulation units); images and particle files are what they are without it
 
-The numeric work is infer.simulate_objects (the operators of SURVEY 8 f3) on the HIP kernels.  Not reproduced: packing the
+The numeric work is infer.simulate_objects (the operators of SURVEY 8 f3) on the HIP kernels; the flags shared with
+`python -m neuma_amd.render`, the output paths and the writers of every product are neuma_amd/frame_outputs.py.  Not reproduced: packing the
 frames into an mp4 (mediapy; --skip_frames / --remove_images are accepted, the latter removes the frames) and the random
 initial velocity of an object without `particle_data.vel` - the reference's own fallback `sample_vel(seed=42)` raises (it
 needs a cfg with lin_vel_bound / ang_vel_bound, nclaw/utils.py:15-30): here such an object samples when its `particle_data`
@@ -52,16 +53,14 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import collider_draw, contact, field_paint, io as nio
+from . import io as nio
 from .config import Cfg, load_config
 from .dataset import CameraDataset
-from .evaluate import save_image
+from .frame_outputs import DrivenMesh, FrameWriter, add_flags
 from .infer import SceneObject, simulate_objects
 from .material import InvariantFullMetaElasticity, InvariantFullMetaPlasticity, build as build_material
 from .prepare import prepare_simulation_data
 from .sim import MPMInitData, MPMModelBuilder
-from .sim.colliders import describe as describe_colliders, describe_fields as describe_field_colliders
-from .tune import denormalize_points_helper_func
 
 RESULT = "results"
 
@@ -72,29 +71,8 @@ def parse_args(argv=None):
     p.add_argument("--eval_steps", "-s", type=int, default=600, help="Number of simulation steps.")
     p.add_argument("--skip_frames", "-f", type=int, default=1, help="Number of skip frames when packing the video.")
     p.add_argument("--remove_images", "-ri", action="store_true", help="Whether to remove images after packing video.")
-    p.add_argument("--video_name", "-vn", type=str, required=True, help="Save video name.")
-    p.add_argument("--debug_views", "-dv", nargs="+", default=[], help="Views for rendering.")
-    p.add_argument("--save_particles", "-sp", type=str, default=None, help="Specify the folder name for saving simulated particles.")
-    p.add_argument("--save_gaussians", type=str, default=None,
-                   help="Write every frame as one 3DGS .ply of all objects into inference/gaussians_<name>/ (python -m neuma_amd.replay).")
-    p.add_argument("--save_mesh", type=str, default=None,
-                   help="Write every frame as one closed triangle mesh of all objects into inference/meshes_<name>/ (neuma_amd/surface_mesh.py).")
-    p.add_argument("--mesh_resolution", type=int, default=128, help="Lattice cells along the longest side of a frame's mesh.")
-    p.add_argument("--mesh_density_thres", type=float, default=0.5,
-                   help="Density level of the mesh surface (default not tuned on a real capture).")
     p.add_argument("--dataset_path", type=str, default=None, help="Rewrite video dataset path.")
-    p.add_argument("--result_root", type=str, default=RESULT)
-    p.add_argument("--rotate_sh", action="store_true", help="Rotate every object's SH colours with its deformation (gaussian.rotate_sh).")
-    p.add_argument("--draw_colliders", action="store_true", help="Draw the colliders of sim.colliders into every frame (sim.draw_colliders).")
-    p.add_argument("--draw_mesh_colliders", action="store_true",
-                   help="Draw the mesh colliders too (sim.draw_mesh_colliders); implies --draw_colliders.")
-    p.add_argument("--report_contacts", action="store_true",
-                   help="Write the force and torque on the walls and on each collider per frame to contacts_<video_name>.csv (sim.report_contacts).")
-    p.add_argument("--color_by", type=str, default=None, choices=field_paint.QUANTITIES,
-                   help="Render every frame a second time, coloured by this particle quantity (color_by).")
-    p.add_argument("--color_range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
-                   help="The value range of the colour map (color_range); default: every frame's own range.")
-    p.add_argument("--colormap", type=str, default=None, choices=sorted(field_paint.COLORMAPS), help="colormap")
+    add_flags(p, RESULT)
     return p.parse_args(argv)
 
 
@@ -185,34 +163,6 @@ def load_object(obj_cfg: Cfg, assets: Path, eval_steps: int, device, rotate_sh: 
                        name=str(obj_cfg.sim_data_name), drive_mesh=obj_cfg.get("drive_mesh"))
 
 
-class _DrivenObject(object):
-    """One object's `drive_mesh`: bound at frame 0 to the object's particles in the frame its Gaussians are rendered in."""
-
-    def __init__(self, obj: SceneObject, offset: int, denormalize: bool, root: Path, device):
-        from . import mesh_drive
-        self.md, self.obj, self.denormalize = mesh_drive, obj, denormalize
-        self.lo, self.hi = offset, offset + int(obj.init_data.num_particles)
-        verts, self.tris, _ = mesh_drive.read_mesh(obj.drive_mesh)
-        self.verts = torch.as_tensor(verts, dtype=torch.float32, device=device)
-        if not denormalize:                          # what scale_gaussians / translate_gaussians do to the centres (infer.py)
-            self.verts = self.verts * float(obj.init_data.size[0])
-            self.verts = self.verts + torch.as_tensor(obj.init_data.center, dtype=torch.float32, device=device)
-        self.root = root / "inference" / f"driven_{obj.name}"
-        self.root.mkdir(parents=True, exist_ok=True)
-        self.driver = None
-
-    def particles(self, x):
-        part = x[self.lo:self.hi]
-        return denormalize_points_helper_func(part, self.obj.init_data.size, self.obj.init_data.center) if self.denormalize else part
-
-    def write(self, step: int, x) -> None:
-        if self.driver is None:
-            self.driver = self.md.MeshDriver(self.verts, self.tris, self.particles(x), device=x.device)
-            print(f"{self.obj.name}: {self.driver.describe()}")
-        pos, nrm = self.driver.rest_frame() if step < int(self.obj.init_data.span[0]) else self.driver.frame(self.particles(x))
-        self.md.save_frame(self.root / f"{step:03d}.ply", pos, nrm, None, self.driver.triangles_np)
-
-
 @torch.no_grad()
 def inference(cfg: Cfg, on_frame=None):
     """inference.py:87-377 (`eval`).  Returns the image folder."""
@@ -221,53 +171,10 @@ def inference(cfg: Cfg, on_frame=None):
     device = torch.device(f"cuda:{cfg.gpu}")
     torch.cuda.set_device(device)
     background = torch.tensor([1.0, 1.0, 1.0] if cfg.video_data.data.get("white_background", False) else [0.0, 0.0, 0.0], device=device)
-    root = Path(cfg.get("result_root", RESULT))
-    image_root = root / "inference" / f"images_{cfg.video_name}"
-    image_root.mkdir(exist_ok=True, parents=True)
-    (root / "inference_videos").mkdir(exist_ok=True)
-    state_root = None
-    if cfg.get("save_particles") is not None:
-        state_root = root / "inference_states" / f"states_{cfg.save_particles}"
-        state_root.mkdir(parents=True, exist_ok=True)
-    gauss_root = None
-    if cfg.get("save_gaussians") is not None:
-        gauss_root = root / "inference" / f"gaussians_{cfg.save_gaussians}"
-        gauss_root.mkdir(parents=True, exist_ok=True)
-    mesh_root = None
-    if cfg.get("save_mesh") is not None:
-        from .surface_mesh import save_surface
-        mesh_root = root / "inference" / f"meshes_{cfg.save_mesh}"
-        mesh_root.mkdir(parents=True, exist_ok=True)
-    painter = field_paint.painter_from_cfg(cfg, cfg.get("gaussian"))
-    paint_root, paint_gauss_root = None, None
-    if painter is not None:
-        paint_root = root / "inference" / f"images_{cfg.video_name}_{painter.quantity}"
-        paint_root.mkdir(exist_ok=True, parents=True)
-        if gauss_root is not None:
-            paint_gauss_root = gauss_root.with_name(f"{gauss_root.name}_{painter.quantity}")
-            paint_gauss_root.mkdir(parents=True, exist_ok=True)
-        print(painter.describe())
+    writer = FrameWriter("inference", cfg, cfg.get("result_root", RESULT))
     eval_steps = int(cfg.eval_steps)
     model = MPMModelBuilder().parse_cfg(cfg.sim).finalize(device, False)          # the YAML's own sim.eps (no override here)
-    draw_styles, mesh_styles = None, None
-    draw_mesh = collider_draw.mesh_wanted(cfg, cfg.sim)                      # implies draw_colliders
-    if collider_draw.wanted(cfg, cfg.sim) or draw_mesh:
-        nodes = list(cfg.sim.get("colliders") or [])
-        if draw_mesh and model.field_colliders:
-            mesh_styles = collider_draw.parse_mesh_styles(nodes[len(model.colliders):], len(model.colliders))
-        if model.colliders or mesh_styles:
-            draw_styles = collider_draw.parse_styles(nodes[:len(model.colliders)])      # (mesh entries follow them)
-        else:
-            print("draw_colliders: sim.colliders is empty, nothing to draw")
-    if model.colliders:
-        print(describe_colliders(model.colliders, drawn=draw_styles is not None))
-    if model.field_colliders:
-        print(describe_field_colliders(model.field_colliders, draw_wanted=collider_draw.wanted(cfg, cfg.sim), drawn=mesh_styles is not None))
-    meter = None
-    if contact.wanted(cfg, cfg.sim):
-        meter = contact.ContactMeter(model)
-        if not (model.colliders or model.field_colliders):
-            print("report_contacts: sim.colliders is empty, reporting the box walls alone")
+    options = writer.loop_options(model)
     if cfg.get("dataset_path") is not None:
         cfg.video_data.data.path = cfg.dataset_path
         print(f"Rewrite video dataset path to\n\t{cfg.dataset_path}")
@@ -276,48 +183,27 @@ def inference(cfg: Cfg, on_frame=None):
         cfg.video_data.data.used_views = debug_views
     cfg.video_data.device = str(device)
     dataset = CameraDataset(cfg.video_data)
-    first_step = dataset.steps[0]
+    first_step = writer.state_offset = dataset.steps[0]
     assets = Path(cfg.get("assets_root", "experiments/assets"))
     objects = [load_object(o, assets, eval_steps, device, rotate_sh=bool(cfg.get("rotate_sh", False))) for o in cfg.objects]
-    driven, offset = [], 0
-    for o in objects:
+    denormalize, offset = bool(cfg.get("denormalize", False)), 0
+    for o in objects:              # a drive_mesh goes through the mapping the object's Gaussian centres go through
+        n, align = int(o.init_data.num_particles), (o.init_data.size, o.init_data.center)
         if o.drive_mesh is not None:
-            driven.append(_DrivenObject(o, offset, bool(cfg.get("denormalize", False)), root, device))
-        offset += int(o.init_data.num_particles)
+            writer.driven.append(DrivenMesh(o.drive_mesh, writer.paths["images"].parent / f"driven_{o.name}", offset, offset + n, device,
+                                            align if denormalize else None, None if denormalize else align,
+                                            first_live=int(o.init_data.span[0]), label=f"{o.name}: "))
+        offset += n
     views = [vw for vw in dataset.views if vw in debug_views]
     cameras = [dataset.getCameras(vw, first_step) for vw in views]               # the camera of the FIRST step throughout
-    for frame in simulate_objects(model, objects, eval_steps, cameras, background, denormalize=bool(cfg.get("denormalize", False)),
-                                  export=gauss_root is not None or mesh_root is not None, draw_styles=draw_styles, draw_mesh_styles=mesh_styles, painter=painter, meter=meter):
-        step = frame["step"]
-        if gauss_root is not None:
-            nio.save_gaussians_ply(frame["gaussians"], gauss_root / f"{step:03d}.ply")
-        if mesh_root is not None:
-            save_surface(mesh_root / f"{step:03d}.ply", frame["gaussians"], int(cfg.get("mesh_resolution") or 128),
-                         float(cfg.get("mesh_density_thres") or 0.5))
-        for d in driven:
-            d.write(step, frame["x"])
-        for vw, img in zip(views, frame["images"]):
-            save_image(img, image_root / f"{vw}_{step:03d}.png")
-        if state_root is not None and step > 0 and painter is None:
-            nio.save_particles_ply(state_root / f"{first_step + step:03d}.ply", frame["x"].detach().cpu().numpy())
-        elif state_root is not None and step > 0:
-            field_paint.save_particles_ply(state_root / f"{first_step + step:03d}.ply", frame["x"], frame["values"], painter.quantity)
-        if painter is not None:
-            for vw, img in zip(views, frame["paint_images"]):
-                save_image(img, paint_root / f"{vw}_{step:03d}.png")
-            if paint_gauss_root is not None:
-                nio.save_gaussians_ply(frame["paint_gaussians"], paint_gauss_root / f"{step:03d}.ply")
+    for frame in simulate_objects(model, objects, eval_steps, cameras, background, denormalize=denormalize, **options):
+        writer.write(frame, views)
         if on_frame is not None:
-            on_frame(step, frame)
-    said = painter.summary() if painter is not None else None
-    if said is not None:
-        print(said)
-    if meter is not None:
-        print(f"contacts: {meter.write_csv(root / 'inference' / f'contacts_{cfg.video_name}.csv')}")
-        print(meter.summary())
+            on_frame(frame["step"], frame)
+    writer.finish()
     if cfg.get("remove_images"):
-        shutil.rmtree(image_root, ignore_errors=True)
-    return image_root
+        shutil.rmtree(writer.paths["images"], ignore_errors=True)
+    return writer.paths["images"]
 
 
 def main(argv=None):
