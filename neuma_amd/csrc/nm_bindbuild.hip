@@ -7,15 +7,13 @@
 // (:253-262); every kept particle gets the same weight 1/n (softmax of -ones, :259-269).
 //
 // The reference evaluates all K x N pairs (one kernel launch per Gaussian over all particles) and materialises a dense
-// K x N fp32 matrix.  Here the particles are binned once into a uniform grid (counting sort with rocPRIM), and a thread
-// per Gaussian visits only the cells under the axis-aligned box of its confidence ellipsoid
+// K x N fp32 matrix.  Here the particles are binned once into a uniform grid (k_bind_cell_keys, rocPRIM pair sort,
+// k_nm_segment_starts of nm_cells.h for every cell's first sorted position), and a thread per Gaussian (k_bind_build)
+// visits only the cells under the axis-aligned box of its confidence ellipsoid
 // (half extent sqrt(chi2 * cov_ii) per axis), keeping the max_particles best candidates in registers.  Output is the
 // padded candidate table (K x max_particles, columns ascending) + the number kept per Gaussian, i.e. CSR after one
 // prefix sum - never a dense matrix.
-#include "nm_common.h"
-#include "nm_workspace.h"
-
-#include <rocprim/rocprim.hpp>
+#include "nm_cells.h"
 
 #define NM_BIND_MAXP 16
 
@@ -25,6 +23,7 @@ struct BindGrid {
   int n[3];        // cells per axis
 };
 
+// (not nm_cell: fp32, the arithmetic of the caller's lattice)
 __device__ __forceinline__ int bind_cell_coord(float x, float o, float inv_h, int n) {
   int c = (int)floorf((x - o) * inv_h);
   return max(0, min(c, n - 1));
@@ -39,20 +38,6 @@ __global__ void __launch_bounds__(256) k_bind_cell_keys(int N, BindGrid g, const
   int cz = bind_cell_coord(x[3 * i + 2], g.o[2], g.inv_h, g.n[2]);
   keys[i] = (uint32_t)((cx * g.n[1] + cy) * g.n[2] + cz);
   vals[i] = (uint32_t)i;
-}
-
-// cell_start[c] = first sorted position of cell c (cell_start[ncells] = N)
-__global__ void __launch_bounds__(256) k_bind_cell_start(int N, int ncells, const uint32_t* __restrict__ keys_sorted,
-                                                         int* __restrict__ cell_start) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i > N) return;
-  uint32_t cur = i < N ? keys_sorted[i] : (uint32_t)ncells;
-  uint32_t prev = i > 0 ? keys_sorted[i - 1] : 0xffffffffu;
-  if (i == 0) {
-    for (uint32_t c = 0; c <= cur && c <= (uint32_t)ncells; ++c) cell_start[c] = 0;
-  } else if (cur != prev) {
-    for (uint32_t c = prev + 1; c <= cur; ++c) cell_start[c] = i;
-  }
 }
 
 __global__ void __launch_bounds__(128) k_bind_build(int K, BindGrid g, const float* __restrict__ means, const float* __restrict__ cov6,
@@ -145,19 +130,12 @@ __global__ void __launch_bounds__(128) k_bind_build(int K, BindGrid g, const flo
   }
 }
 
-struct BindWs { uint32_t *keys_in, *keys_out, *vals_in, *vals_out; int* cell_start; void* sort_tmp; size_t sort_bytes; size_t total; };
+struct BindWs { NmSortPairs32 sort; int* cell_start; size_t total; };      // (cell key, particle) pairs; cell_start[c] .. [c + 1]
 static BindWs carve_bind_ws(void* base, int N, int ncells) {
-  BindWs w; NmCarver c(base); size_t n = (size_t)(N > 0 ? N : 1);
-  w.keys_in = c.take<uint32_t>(n);
-  w.keys_out = c.take<uint32_t>(n);
-  w.vals_in = c.take<uint32_t>(n);
-  w.vals_out = c.take<uint32_t>(n);
+  BindWs w; NmCarver c(base);
+  w.sort.carve(c, (size_t)(N > 0 ? N : 1));
+  if (w.sort.bytes == 0) c.off -= 256;      // this size rule has no one-byte minimum: a sort without temporary storage takes no slot
   w.cell_start = c.take<int>((size_t)ncells + 2);
-  size_t tb = 0;
-  rocprim::radix_sort_pairs(nullptr, tb, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0u, 32u,
-                            (hipStream_t)0);
-  w.sort_bytes = tb;
-  w.sort_tmp = c.take<char>(tb);
   w.total = c.total();
   return w;
 }
@@ -187,16 +165,12 @@ extern "C" int nm_bind_build(int32_t K, int32_t N, const float* means, const flo
   g.inv_h = 1.f / cell;
   if (N > 0) {
     NM_REQUIRE(particles, "null particles");
-    NM_LAUNCH(k_bind_cell_keys, dim3(nm_div_up(N, 256)), dim3(256), 0, s, N, g, particles, w.keys_in, w.vals_in);
+    NM_LAUNCH(k_bind_cell_keys, dim3(nm_div_up(N, 256)), dim3(256), 0, s, N, g, particles, w.sort.key_in, w.sort.val_in);
     NM_LAUNCH_CHECK();
-    int bits = 1;
-    while (((int64_t)1 << bits) < nc64) ++bits;
-    size_t tb = w.sort_bytes;
-    NM_HIP_CHECK(rocprim::radix_sort_pairs(w.sort_tmp, tb, w.keys_in, w.keys_out, w.vals_in, w.vals_out, (size_t)N, 0u, (unsigned)bits, s));
+    if (int rc = w.sort.run((size_t)N, nm_key_bits(nc64), s)) return rc;
   }
-  NM_LAUNCH(k_bind_cell_start, dim3(nm_div_up((int64_t)N + 1, 256)), dim3(256), 0, s, N, ncells, w.keys_out, w.cell_start);
-  NM_LAUNCH_CHECK();
-  NM_LAUNCH(k_bind_build, dim3(nm_div_up(K, 128)), dim3(128), 0, s, K, g, means, cov6, particles, w.vals_out, w.cell_start, threshold,
+  if (int rc = nm_segment_starts<NmKeyItself>(w.sort.key_out, N, ncells, w.cell_start, s)) return rc;
+  NM_LAUNCH(k_bind_build, dim3(nm_div_up(K, 128)), dim3(128), 0, s, K, g, means, cov6, particles, w.sort.val_out, w.cell_start, threshold,
                      max_particles, counts, n_inside, cols, pvals);
   NM_LAUNCH_CHECK();
   return NM_OK;

@@ -15,11 +15,8 @@
 //                     observation chose (n = 1) is one wave's work.  Writes the gradient row, a(i), and (thread 0) the loss word
 // Differences and sums in fp64, one fp32 rounding per output, no float atomics: the order of every sum depends on the segment
 // alone, two calls give the same bits.  Coordinates are read and gradients written one float at a time: alignment plays no part.
-#include "nm_common.h"
+#include "nm_cells.h"
 #include "nm_reduce.h"
-#include "nm_workspace.h"
-
-#include <rocprim/rocprim.hpp>
 
 namespace {
 
@@ -35,9 +32,7 @@ struct ClWs {
   double* cd;             // 2: term_xy, term_yx
   int64_t* ia;            // n: a(i), compacted numbering of i
   int64_t* ib;            // m: b(j), compacted numbering
-  uint32_t *key_in, *key_out, *val_in, *val_out;      // m each
-  void* sort_tmp;
-  size_t sort_bytes;
+  NmSortPairs32 sort;     // m pairs (b(j), j)
   char* chamfer;          // nm_chamfer_workspace(1, n, m)
   size_t chamfer_bytes;
 };
@@ -55,15 +50,7 @@ static ClWs carve_cl(NmCarver& c, int n, int m) {
   w.cd = c.take<double>(2);
   w.ia = c.take<int64_t>(n);
   w.ib = c.take<int64_t>(m);
-  w.key_in = c.take<uint32_t>(m);
-  w.key_out = c.take<uint32_t>(m);
-  w.val_in = c.take<uint32_t>(m);
-  w.val_out = c.take<uint32_t>(m);
-  tb = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, tb, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                  (size_t)m, 0u, 32u, (hipStream_t)0);
-  w.sort_bytes = tb;
-  w.sort_tmp = c.take<char>(tb > 0 ? tb : 1);
+  w.sort.carve(c, (size_t)m);
   w.chamfer_bytes = nm_chamfer_workspace(1, n, m);      // (k <= n rows are searched: the arrays of n rows hold them)
   w.chamfer = c.take<char>(w.chamfer_bytes);
   return w;
@@ -206,15 +193,12 @@ extern "C" int nm_chamfer_loss(int32_t n, int32_t m, const float* x, const float
   }
   int rc = nm_chamfer(1, k, m, xs, y, w.cd, w.cd + 1, w.ia, w.ib, w.chamfer, w.chamfer_bytes, stream);
   if (rc != NM_OK) return rc;
-  NM_LAUNCH(k_cl_keys, dim3(nm_div_up(m, kClThreads)), dim3(kClThreads), 0, s, (int)m, (const int64_t*)w.ib, orig, w.key_in, w.val_in,
-            idx_yx);
+  NM_LAUNCH(k_cl_keys, dim3(nm_div_up(m, kClThreads)), dim3(kClThreads), 0, s, (int)m, (const int64_t*)w.ib, orig, w.sort.key_in,
+            w.sort.val_in, idx_yx);
   NM_LAUNCH_CHECK();
-  unsigned bits = 1;
-  while (((int64_t)1 << bits) < (int64_t)k) ++bits;
-  size_t tb = w.sort_bytes;
-  NM_HIP_CHECK(rocprim::radix_sort_pairs(w.sort_tmp, tb, w.key_in, w.key_out, w.val_in, w.val_out, (size_t)m, 0u, bits, s));
+  if ((rc = w.sort.run((size_t)m, nm_key_bits(k), s)) != NM_OK) return rc;
   NM_LAUNCH(k_cl_rows, dim3(nm_div_up(k, kClThreads)), dim3(kClThreads), 0, s, k, (int)m, weight_xy, weight_yx, xs, y,
-            (const int64_t*)w.ia, (const uint32_t*)w.key_out, (const uint32_t*)w.val_out, orig, (const double*)w.cd, dL_dx, idx_xy,
+            (const int64_t*)w.ia, (const uint32_t*)w.sort.key_out, (const uint32_t*)w.sort.val_out, orig, (const double*)w.cd, dL_dx, idx_xy,
             loss_out, terms_out);
   NM_LAUNCH_CHECK();
   return NM_OK;

@@ -19,7 +19,7 @@
 //   exclusive scan of the counts (rocPRIM), k_fill_pairs writes the keys (block << 32) | k, radix sort of the keys
 //                      (rocPRIM): every block's list is contiguous and in ascending Gaussian index, whatever order the
 //                      pairs were written in
-//   k_fill_block_start first sorted position of every block
+//   k_nm_segment_starts (nm_cells.h) first sorted position of every block, from the keys' high words
 //   k_fill_density     one wave per block; its Gaussians (10 floats each: mu, the six entries of inv(Sigma), o) go through
 //                      LDS NM_FILL_BATCH at a time, every lane adds its cell's terms in list order; a block with an empty
 //                      list writes zeros, so the field needs no clear
@@ -29,10 +29,7 @@
 // Every index that comes from a float is clamped to the lattice before it addresses anything.  The file is compiled with
 // -ffp-contract=off: the fp64 expressions (box, cell centre, emitted coordinate) must round as numpy's do.  The fp32 inner
 // loop of k_fill_density alone opts back into contraction: its result is held to a tolerance, not to bits.
-#include "nm_common.h"
-#include "nm_workspace.h"
-
-#include <rocprim/rocprim.hpp>
+#include "nm_cells.h"
 
 #define NM_FILL_BATCH 64
 #define NM_FILL_BLOCK 4          // cells per block edge (4^3 = 64 = one wave)
@@ -46,6 +43,7 @@ struct FillGrid {
 };
 
 // cell coordinate of x (fp64), clamped to the lattice BEFORE the conversion to int
+// (not nm_cell: it divides by h in fp64 and so rounds as numpy's lattice helper does)
 __device__ __forceinline__ int fill_cell_coord(double x, double o, double h, int n) {
   double c = floor((x - o) / h);
   c = c < 0.0 ? 0.0 : c;                      // (NaN fails both comparisons and is caught by the next line)
@@ -106,21 +104,6 @@ __global__ void __launch_bounds__(256) k_fill_pairs(int K, FillGrid g, const int
         if (at < 0 || at >= n_pairs) return;      // counts and n_pairs that do not belong together never write outside
         keys[at++] = ((uint64_t)(uint32_t)((bx * g.nb[1] + by) * g.nb[2] + bz) << 32) | (uint32_t)k;
       }
-}
-
-// block_start[b] = first sorted position of block b (block_start[nblocks] = n_pairs)
-__global__ void __launch_bounds__(256) k_fill_block_start(long long n_pairs, int nblocks, const uint64_t* __restrict__ keys_sorted,
-                                                          int* __restrict__ block_start) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i > n_pairs) return;
-  const uint32_t nbk = (uint32_t)nblocks;
-  uint32_t cur = i < n_pairs ? min((uint32_t)(keys_sorted[i] >> 32), nbk) : nbk;
-  if (i == 0) {
-    for (uint32_t b = 0; b <= cur; ++b) block_start[b] = 0;
-  } else {
-    uint32_t prev = min((uint32_t)(keys_sorted[i - 1] >> 32), nbk);
-    for (uint32_t b = prev + 1; b <= cur; ++b) block_start[b] = (int)i;
-  }
 }
 
 __global__ void __launch_bounds__(64) k_fill_density(int K, FillGrid g, const int* __restrict__ block_start,
@@ -254,7 +237,7 @@ extern "C" int nm_fill_gaussians(int32_t K, const float* means, const float* cov
   return NM_OK;
 }
 
-struct FillWs { int* offsets; int* block_start; uint64_t *keys_in, *keys_out; void* tmp; size_t tmp_bytes; size_t total; };
+struct FillWs { int* offsets; int* block_start; uint64_t *keys_in, *keys_out; NmIntScan scan; size_t total; };
 static FillWs carve_fill_ws(void* base, int K, int64_t n_pairs, int nblocks) {
   FillWs w; NmCarver c(base);
   const size_t np = (size_t)(n_pairs > 0 ? n_pairs : 1);
@@ -262,11 +245,9 @@ static FillWs carve_fill_ws(void* base, int K, int64_t n_pairs, int nblocks) {
   w.block_start = c.take<int>((size_t)nblocks + 2);
   w.keys_in = c.take<uint64_t>(np);
   w.keys_out = c.take<uint64_t>(np);
-  size_t sort_b = 0, scan_b = 0;
+  size_t sort_b = 0;      // the scan of the counts and the key sort run one after the other in one temporary region
   rocprim::radix_sort_keys(nullptr, sort_b, (uint64_t*)nullptr, (uint64_t*)nullptr, np, 0u, 64u, (hipStream_t)0);
-  rocprim::exclusive_scan(nullptr, scan_b, (int*)nullptr, (int*)nullptr, 0, (size_t)K, rocprim::plus<int>(), (hipStream_t)0);
-  w.tmp_bytes = sort_b > scan_b ? sort_b : scan_b;
-  w.tmp = c.take<char>(w.tmp_bytes > 0 ? w.tmp_bytes : 1);
+  w.scan.carve(c, (size_t)K, sort_b);
   w.total = c.total();
   return w;
 }
@@ -294,27 +275,23 @@ extern "C" int nm_fill_density(int32_t K, int64_t n_pairs, const float* g10, con
     return NM_ERR_WORKSPACE;
   }
   hipStream_t s = (hipStream_t)stream;
-  size_t tb = w.tmp_bytes;
-  NM_HIP_CHECK(rocprim::exclusive_scan(w.tmp, tb, counts, w.offsets, 0, (size_t)K, rocprim::plus<int>(), s));
+  if (int rc = w.scan.run(counts, w.offsets, (size_t)K, s)) return rc;
   const uint64_t* sorted = w.keys_in;
   if (n_pairs > 0) {
     NM_LAUNCH(k_fill_pairs, dim3(nm_div_up(K, 256)), dim3(256), 0, s, K, g, boxes, counts, (const int*)w.offsets, (long long)n_pairs,
               w.keys_in);
     NM_LAUNCH_CHECK();
-    unsigned bits = 1;
-    while (((int64_t)1 << bits) < nblocks) ++bits;
-    tb = w.tmp_bytes;
-    NM_HIP_CHECK(rocprim::radix_sort_keys(w.tmp, tb, w.keys_in, w.keys_out, (size_t)n_pairs, 0u, 32u + bits, s));
+    size_t tb = w.scan.bytes;
+    NM_HIP_CHECK(rocprim::radix_sort_keys(w.scan.tmp, tb, w.keys_in, w.keys_out, (size_t)n_pairs, 0u, 32u + nm_key_bits(nblocks), s));
     sorted = w.keys_out;
   }
-  NM_LAUNCH(k_fill_block_start, dim3(nm_div_up(n_pairs + 1, 256)), dim3(256), 0, s, (long long)n_pairs, nblocks, sorted, w.block_start);
-  NM_LAUNCH_CHECK();
+  if (int rc = nm_segment_starts<NmKeyHighWord>(sorted, n_pairs, nblocks, w.block_start, s)) return rc;
   NM_LAUNCH(k_fill_density, dim3(nblocks), dim3(64), 0, s, K, g, (const int*)w.block_start, sorted, g10, cutoff, field);
   NM_LAUNCH_CHECK();
   return NM_OK;
 }
 
-struct FillCws { int *first[3], *last[3]; int* keep; void* tmp; size_t tmp_bytes; size_t total; };
+struct FillCws { int *first[3], *last[3]; int* keep; NmIntScan scan; size_t total; };
 static FillCws carve_fill_cws(void* base, const int32_t* dims) {
   FillCws w; NmCarver c(base);
   const size_t nc = (size_t)dims[0] * dims[1] * dims[2];
@@ -324,10 +301,7 @@ static FillCws carve_fill_cws(void* base, const int32_t* dims) {
     w.last[a] = c.take<int>(lines);
   }
   w.keep = c.take<int>(nc);
-  size_t tb = 0;
-  rocprim::exclusive_scan(nullptr, tb, (int*)nullptr, (int*)nullptr, 0, nc, rocprim::plus<int>(), (hipStream_t)0);
-  w.tmp_bytes = tb;
-  w.tmp = c.take<char>(tb > 0 ? tb : 1);
+  w.scan.carve(c, nc);
   w.total = c.total();
   return w;
 }
@@ -364,9 +338,7 @@ extern "C" int nm_fill_classify(const int32_t* dims, const float* field, float d
             include_shell ? 1 : 0, (const int*)w.first[0], (const int*)w.last[0], (const int*)w.first[1], (const int*)w.last[1],
             (const int*)w.first[2], (const int*)w.last[2], kind_cell, w.keep, counts);
   NM_LAUNCH_CHECK();
-  size_t tb = w.tmp_bytes;
-  NM_HIP_CHECK(rocprim::exclusive_scan(w.tmp, tb, w.keep, offsets, 0, nc, rocprim::plus<int>(), s));
-  return NM_OK;
+  return w.scan.run(w.keep, offsets, nc, s);
 }
 
 extern "C" int nm_fill_emit(const int32_t* dims, const double* origin, double h, int32_t per_cell, int32_t include_shell,

@@ -4,8 +4,8 @@
 // its own cell:
 //   k_mi_prep     one thread per triangle: index check, the operands the test reads (d included), the `ok` filter, a
 //                 conservative xy box (below), and a partial xy box of the mesh per workgroup
-//   k_mi_grid     one workgroup: finish of the partials -> origin, cells per axis (within a cell budget that depends on the
-//                 triangle count only, so the host sizes the workspace without reading the data), cells per unit length
+//   k_mi_grid     one workgroup: finish of the partials -> the mesh's xy box and its cells (nm_cells_fit of nm_cells.h, within
+//                 a cell budget that depends on the triangle count only, so the host sizes the workspace without reading the data)
 //   k_mi_count    cell range of every triangle's box, per-cell counters (integer atomics).  A triangle whose box covers more
 //                 than kMaxCells cells, whose cells no longer fit the pair capacity, or that has no finite box, goes to the
 //                 list that every point walks instead
@@ -18,11 +18,8 @@
 //
 // The formula is evaluated as numpy evaluates it, one rounded operation at a time: no contraction into fma (numpy does not
 // fuse; the Makefile also passes -ffp-contract=off for this file), and fp64 `/` is the correctly rounded division.
-#include "nm_common.h"
+#include "nm_cells.h"
 #include "nm_reduce.h"
-#include "nm_workspace.h"
-
-#include <rocprim/rocprim.hpp>
 
 #pragma clang fp contract(off)
 
@@ -47,11 +44,7 @@ struct MiBoxPart {
   double lo[2], hi[2];
 };
 
-struct MiGrid {
-  double o[2];       // origin of cell 0
-  double inv_h[2];   // cells per unit length (0 on a one-cell axis)
-  int n[2];          // cells per axis, n0 * n1 <= the cell budget
-};
+using MiGrid = NmCells<2>;      // boxes and points alike go through nm_cell
 
 // per-triangle state between the passes (0 = boxed, not yet placed)
 enum : int { kTriDropped = -1, kTriAll = -2, kTriBinned = 1 };
@@ -77,8 +70,7 @@ struct MiWs {
   int* start;                  // their exclusive scan
   int* pairs;                  // cap triangle ids, by cell
   int* all;                    // T triangle ids
-  void* scan_tmp;
-  size_t scan_bytes;
+  NmIntScan scan;
   size_t total;
 };
 
@@ -98,10 +90,7 @@ static MiWs carve(void* base, int t) {
   w.start = c.take<int>(nc);
   w.pairs = c.take<int>((size_t)w.cap);
   w.all = c.take<int>(nt);
-  size_t tb = 0;
-  rocprim::exclusive_scan(nullptr, tb, (int*)nullptr, (int*)nullptr, 0, nc, rocprim::plus<int>(), (hipStream_t)0);
-  w.scan_bytes = tb;
-  w.scan_tmp = c.take<char>(tb > 0 ? tb : 1);
+  w.scan.carve(c, nc);
   w.total = c.total();
   return w;
 }
@@ -184,48 +173,10 @@ __global__ void __launch_bounds__(kMiThreads) k_mi_grid(int gprep, int cmax, con
   }
   const auto tot = nm_block_reduce<NW, NmMinMax<2>>(bb, red);
   if (threadIdx.x != 0) return;
-  double lo[2], e[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    lo[j] = tot[j];
-    const double hi = tot[2 + j];
-    e[j] = lo[j] <= hi ? hi - lo[j] : 0.0;                     // (no boxed triangle: one cell)
-    if (!mi_finite(lo[j])) lo[j] = 0.0;
-    if (!mi_finite(e[j])) e[j] = 0.0;                          // (a span beyond the fp64 range: one cell on that axis)
-  }
-  double h;
-  if (e[0] > 0.0 && e[1] > 0.0) {
-    h = sqrt(e[0] / (double)cmax * e[1]);
-    if (e[0] < h) h = e[1] / (double)cmax;                     // one column of cells
-    else if (e[1] < h) h = e[0] / (double)cmax;                // one row
-  } else {
-    h = fmax(e[0], e[1]) / (double)cmax;
-  }
+  double lo[2] = {tot[0], tot[1]}, hi[2] = {tot[2], tot[3]}, e[2];
   MiGrid G;
-  int64_t prod = 1;
-  for (int j = 0; j < 2; ++j) {
-    double nj = e[j] > 0.0 && h > 0.0 ? floor(e[j] / h) : 1.0;
-    nj = fmin(fmax(nj, 1.0), (double)cmax);
-    G.n[j] = (int)nj;
-    prod *= G.n[j];
-  }
-  while (prod > cmax) {                                        // (rounding) shrink the longer axis until within budget
-    const int j = G.n[0] >= G.n[1] ? 0 : 1;
-    G.n[j] -= G.n[j] / 64 > 1 ? G.n[j] / 64 : 1;
-    prod = (int64_t)G.n[0] * G.n[1];
-  }
-  for (int j = 0; j < 2; ++j) {
-    G.o[j] = lo[j];
-    G.inv_h[j] = e[j] > 0.0 ? (double)G.n[j] / e[j] : 0.0;
-  }
+  nm_cells_fit(lo, hi, cmax, G, e);                            // (no boxed triangle, or a span beyond the fp64 range: one cell)
   *grid = G;
-}
-
-// the one monotone map from a coordinate to its cell, for boxes and points alike (NaN -> 0, +-Inf -> an edge cell)
-__device__ __forceinline__ int mi_cell(double x, double o, double inv_h, int n) {
-  double f = floor((x - o) * inv_h);
-  f = fmin(fmax(f, 0.0), (double)(n - 1));
-  return (int)f;
 }
 
 __global__ void __launch_bounds__(kMiThreads) k_mi_count(int T, long long cap, const double4* __restrict__ box,
@@ -240,8 +191,8 @@ __global__ void __launch_bounds__(kMiThreads) k_mi_count(int T, long long cap, c
   if (st == 0) {
     const MiGrid G = *grid;
     const double4 b = box[t];
-    const int x0 = mi_cell(b.x, G.o[0], G.inv_h[0], G.n[0]), x1 = mi_cell(b.z, G.o[0], G.inv_h[0], G.n[0]);
-    const int y0 = mi_cell(b.y, G.o[1], G.inv_h[1], G.n[1]), y1 = mi_cell(b.w, G.o[1], G.inv_h[1], G.n[1]);
+    const int x0 = nm_cell(b.x, G.o[0], G.inv_h[0], G.n[0]), x1 = nm_cell(b.z, G.o[0], G.inv_h[0], G.n[0]);
+    const int y0 = nm_cell(b.y, G.o[1], G.inv_h[1], G.n[1]), y1 = nm_cell(b.w, G.o[1], G.inv_h[1], G.n[1]);
     const int nc = (x1 - x0 + 1) * (y1 - y0 + 1);
     if (nc <= kMaxCells && (long long)(atomicAdd(used, (unsigned long long)nc) + nc) <= cap) {
       binned = true;
@@ -264,8 +215,8 @@ __global__ void __launch_bounds__(kMiThreads) k_mi_scatter(int T, const double4*
   if (t >= T || state[t] != kTriBinned) return;
   const MiGrid G = *grid;
   const double4 b = box[t];
-  const int x0 = mi_cell(b.x, G.o[0], G.inv_h[0], G.n[0]), x1 = mi_cell(b.z, G.o[0], G.inv_h[0], G.n[0]);
-  const int y0 = mi_cell(b.y, G.o[1], G.inv_h[1], G.n[1]), y1 = mi_cell(b.w, G.o[1], G.inv_h[1], G.n[1]);
+  const int x0 = nm_cell(b.x, G.o[0], G.inv_h[0], G.n[0]), x1 = nm_cell(b.z, G.o[0], G.inv_h[0], G.n[0]);
+  const int y0 = nm_cell(b.y, G.o[1], G.inv_h[1], G.n[1]), y1 = nm_cell(b.w, G.o[1], G.inv_h[1], G.n[1]);
   for (int x = x0; x <= x1; ++x)
     for (int y = y0; y <= y1; ++y) {
       const int c = x * G.n[1] + y;
@@ -292,7 +243,7 @@ __global__ void __launch_bounds__(kMiThreads) k_mi_query(int P, const double* __
   if (i >= P) return;
   const double px = pts[3 * (size_t)i], py = pts[3 * (size_t)i + 1], pz = pts[3 * (size_t)i + 2];
   const MiGrid G = *grid;
-  const int c = mi_cell(px, G.o[0], G.inv_h[0], G.n[0]) * G.n[1] + mi_cell(py, G.o[1], G.inv_h[1], G.n[1]);
+  const int c = nm_cell(px, G.o[0], G.inv_h[0], G.n[0]) * G.n[1] + nm_cell(py, G.o[1], G.inv_h[1], G.n[1]);
   int hits = 0;
   const int s = start[c], e = start[c + 1];
   for (int k = s; k < e; ++k) hits += mi_hit(rec[pairs[k]], px, py, pz);
@@ -335,8 +286,7 @@ extern "C" int nm_points_in_mesh(int32_t n_verts, int32_t n_tris, int32_t n_poin
   NM_LAUNCH(k_mi_count, tg, dim3(kMiThreads), 0, s, n_tris, (long long)w.cap, (const double4*)w.box, (const MiGrid*)w.grid, w.state,
             w.cnt, w.used, w.nall, w.all);
   NM_LAUNCH_CHECK();
-  size_t tb = w.scan_bytes;
-  NM_HIP_CHECK(rocprim::exclusive_scan(w.scan_tmp, tb, w.cnt, w.start, 0, nc, rocprim::plus<int>(), s));
+  if (int rc = w.scan.run(w.cnt, w.start, nc, s)) return rc;
   NM_LAUNCH(k_mi_scatter, tg, dim3(kMiThreads), 0, s, n_tris, (const double4*)w.box, (const MiGrid*)w.grid, (const int*)w.state,
             (const int*)w.start, w.cnt, w.pairs);
   NM_LAUNCH_CHECK();

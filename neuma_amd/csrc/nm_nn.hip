@@ -3,8 +3,9 @@
 //
 // Each cloud is binned once, per batch item, into a uniform grid over its own bounding box:
 //   k_nn_box      partial min / max of the finite coordinates and a count of non-finite ones, one per workgroup
-//   k_nn_grid     one thread per item: finish of the partials -> origin, cells per axis (within a cell budget that depends on
-//                 the cloud's size only, so the host sizes the workspace without knowing the data), cell edge per axis
+//   k_nn_grid     one thread per item: finish of the partials -> the box, its cells (nm_cells_fit of nm_cells.h, within a cell
+//                 budget that depends on the cloud's size only, so the host sizes the workspace without knowing the data),
+//                 cell edge per axis
 //   k_nn_count    cell key of every point, and its rank inside its cell (integer atomics on the cell counters)
 //   (rocPRIM exclusive scan of the counters: every cell's first position in the sorted array)
 //   k_nn_scatter  the cloud sorted by cell as float4 {x, y, z, index}
@@ -17,11 +18,8 @@
 // the fixed order of nm_reduce.h over the queries in their ORIGINAL order (k_nn_mean_part, k_nn_mean_finish).
 // The k-NN search (k_nn_search_k, 1 <= k <= 16: nm_knn, and nm_knn_mean_dist2 = simple_knn's distCUDA2 at k = 3) is the same
 // walk with a k-best list per thread in registers; it stops on the k-th best instead of the best.
-#include "nm_common.h"
+#include "nm_cells.h"
 #include "nm_reduce.h"
-#include "nm_workspace.h"
-
-#include <rocprim/rocprim.hpp>
 
 namespace {
 
@@ -36,7 +34,9 @@ struct NnBoxPart {
   int pad;
 };
 
-struct NnGrid {          // one per (cloud, item), written by k_nn_grid
+// One per (cloud, item), written by k_nn_grid.  o, inv_h and n are an NmCells<3>'s fields, copied: as a member its padded
+// 64 bytes would make this 144 bytes, not 136, and the workspace sizes are part of the interface.
+struct NnGrid {
   double o[3];           // box minimum (origin of cell 0)
   double inv_h[3];       // cells per unit length (0 on a one-cell axis)
   double h[3];           // cell edge
@@ -45,6 +45,7 @@ struct NnGrid {          // one per (cloud, item), written by k_nn_grid
   int n[3];              // cells per axis, n0 * n1 * n2 <= the cell budget
   int bad;               // the cloud holds a NaN / Inf coordinate in this item
 };
+static_assert(sizeof(NnGrid) == 136, "nm_nn_workspace depends on it");
 
 static inline int nn_box_blocks(int p) {
   const int g = nm_div_up(p, kNnThreads * 8);
@@ -66,8 +67,7 @@ struct NnBin {
   int* key;          // B * P
   int* rank;         // B * P
   float4* sorted;    // B * P
-  void* scan_tmp;
-  size_t scan_bytes;
+  NmIntScan scan;
 };
 
 static NnBin carve_bin(NmCarver& c, int b, int p) {
@@ -81,10 +81,7 @@ static NnBin carve_bin(NmCarver& c, int b, int p) {
   w.key = c.take<int>(np);          // key + rank: nm_chamfer may reuse the pair as B * P int64
   w.rank = c.take<int>(np);
   w.sorted = c.take<float4>(np);
-  size_t tb = 0;
-  rocprim::exclusive_scan(nullptr, tb, (int*)nullptr, (int*)nullptr, 0, nc, rocprim::plus<int>(), (hipStream_t)0);
-  w.scan_bytes = tb;
-  w.scan_tmp = c.take<char>(tb > 0 ? tb : 1);
+  w.scan.carve(c, nc);
   return w;
 }
 
@@ -122,72 +119,33 @@ __global__ void __launch_bounds__(kNnThreads) k_nn_box(int P, int gbox, const fl
   }
 }
 
-// one thread per item: the box, then the cells.  An axis shorter than the cubic cell edge h (zero extent included) gets one
-// cell and h is recomputed over the other axes; then n_i = floor(e_i / h), so n0 n1 n2 <= cmax.
+// one thread per item: the box, then its cells
 __global__ void __launch_bounds__(64) k_nn_grid(int B, int gbox, int cmax, const NnBoxPart* __restrict__ part, NnGrid* __restrict__ grid) {
   const int item = blockIdx.x * 64 + threadIdx.x;
   if (item >= B) return;
-  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  int bad = 0;
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, e[3];
+  NnGrid G;
+  G.bad = 0;
   for (int g = 0; g < gbox; ++g) {
     const NnBoxPart& r = part[(size_t)item * gbox + g];
-    for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], r.lo[k]); hi[k] = fmaxf(hi[k], r.hi[k]); }
-    bad += r.bad;
+    for (int k = 0; k < 3; ++k) { lo[k] = fmin(lo[k], (double)r.lo[k]); hi[k] = fmax(hi[k], (double)r.hi[k]); }
+    G.bad += r.bad;
   }
-  NnGrid G;
-  double e[3];
-  bool active[3];
+  NmCells<3> c;
+  nm_cells_fit(lo, hi, cmax, c, e);
   for (int k = 0; k < 3; ++k) {
-    if (!(lo[k] <= hi[k])) { lo[k] = 0.f; hi[k] = 0.f; }        // no finite point at all
-    G.o[k] = (double)lo[k];
-    G.hi[k] = (double)hi[k];
-    e[k] = (double)hi[k] - (double)lo[k];
-    active[k] = e[k] > 0.0;
-  }
-  double h = 0.0;
-  for (int it = 0; it < 3; ++it) {
-    int d = 0;
-    double vol = 1.0;
-    for (int k = 0; k < 3; ++k)
-      if (active[k]) { ++d; vol *= e[k]; }
-    if (d == 0) break;
-    h = pow(vol / (double)cmax, 1.0 / d);
-    bool changed = false;
-    for (int k = 0; k < 3; ++k)
-      if (active[k] && e[k] < h) { active[k] = false; changed = true; }
-    if (!changed) break;
-  }
-  int64_t prod = 1;
-  for (int k = 0; k < 3; ++k) {
-    double nk = active[k] && h > 0.0 ? floor(e[k] / h) : 1.0;
-    nk = fmin(fmax(nk, 1.0), (double)cmax);
-    G.n[k] = (int)nk;
-    prod *= G.n[k];
-  }
-  while (prod > cmax) {                                          // (pow's rounding) shrink the longest axis until within budget
-    int k = G.n[0] >= G.n[1] ? (G.n[0] >= G.n[2] ? 0 : 2) : (G.n[1] >= G.n[2] ? 1 : 2);
-    G.n[k] -= G.n[k] / 64 > 1 ? G.n[k] / 64 : 1;
-    prod = (int64_t)G.n[0] * G.n[1] * G.n[2];
-  }
-  for (int k = 0; k < 3; ++k) {
-    G.inv_h[k] = e[k] > 0.0 ? (double)G.n[k] / e[k] : 0.0;
+    G.o[k] = c.o[k]; G.inv_h[k] = c.inv_h[k]; G.n[k] = c.n[k];
+    G.hi[k] = hi[k];
     G.h[k] = e[k] / (double)G.n[k];
     G.slack[k] = 1e-9 * (fabs(G.o[k]) + fabs(G.hi[k])) + 1e-300;
   }
-  G.bad = bad;
   grid[item] = G;
 }
 
-__device__ __forceinline__ int nn_cell(double x, double o, double inv_h, int n) {
-  double f = floor((x - o) * inv_h);
-  f = fmin(fmax(f, 0.0), (double)(n - 1));      // NaN -> 0: every input lands in a cell of the grid
-  return (int)f;
-}
-
 __device__ __forceinline__ int nn_key(const NnGrid& G, float x, float y, float z) {
-  const int cx = nn_cell(x, G.o[0], G.inv_h[0], G.n[0]);
-  const int cy = nn_cell(y, G.o[1], G.inv_h[1], G.n[1]);
-  const int cz = nn_cell(z, G.o[2], G.inv_h[2], G.n[2]);
+  const int cx = nm_cell(x, G.o[0], G.inv_h[0], G.n[0]);
+  const int cy = nm_cell(y, G.o[1], G.inv_h[1], G.n[1]);
+  const int cz = nm_cell(z, G.o[2], G.inv_h[2], G.n[2]);
   return (cx * G.n[1] + cy) * G.n[2] + cz;
 }
 
@@ -291,7 +249,7 @@ __device__ __forceinline__ void nn_walk(const float4& q, const NnGrid& G, const 
   double out2[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    c[k] = nn_cell(qv[k], G.o[k], G.inv_h[k], G.n[k]);
+    c[k] = nm_cell(qv[k], G.o[k], G.inv_h[k], G.n[k]);
     out2[k] = nn_out2(qv[k], G.o[k], G.hi[k], G.slack[k]);
   }
   const int rmax = max(n0, max(n1, n2));
@@ -413,8 +371,7 @@ static int nn_bin(const NnBin& w, const float* pts, hipStream_t s) {
   const dim3 pg(nm_div_up(w.p, kNnThreads), w.b);
   NM_LAUNCH(k_nn_count, pg, dim3(kNnThreads), 0, s, w.p, w.cmax, pts, (const NnGrid*)w.grid, w.cnt, w.key, w.rank);
   NM_LAUNCH_CHECK();
-  size_t tb = w.scan_bytes;
-  NM_HIP_CHECK(rocprim::exclusive_scan(w.scan_tmp, tb, w.cnt, w.start, 0, nc, rocprim::plus<int>(), s));
+  if (int rc = w.scan.run(w.cnt, w.start, nc, s)) return rc;
   NM_LAUNCH(k_nn_scatter, pg, dim3(kNnThreads), 0, s, w.p, w.cmax, pts, (const int*)w.start, (const int*)w.key, (const int*)w.rank,
             w.sorted);
   NM_LAUNCH_CHECK();
