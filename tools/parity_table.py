@@ -19,6 +19,8 @@ def group(case: str) -> str:
     case = re.sub(r"(jelly|plasticine|sand) checkpoint", "<3 checkpoints>", case)
     case = re.sub(r", (elasticity|plasticity),", ",", case)
     case = re.sub(r"world=\d, cap=\w+, ", "<world 2, 3>, ", case)
+    case = re.sub(r"\b(lane|bind)_(samecol_)?[rk]\d+(\^T)?", "<structures>", case)       # tests/test_gpu_frame_tail.py
+    case = re.sub(r"^(nm_pixel_loss|tune\.l[12]_loss), (.*), \d+x\d+$", r"\1, \2, <shapes>", case)
     return re.sub(r"\s+", " ", case).strip()
 
 
