@@ -23,19 +23,32 @@ def _runtime(name="tiny", fused=True, **over):
     return SceneRuntime(scene, dev(), fused=fused)
 
 
-def _oracle_rollout(rt, S, x, v, C, F):
-    """fp64 chain stress=E(F); sim; F=P(F) with the runtime's merged weights (finetune.py:362-364)."""
+def _oracle_rollout(rt, S, x, v, C, F, dtype=torch.float64):
+    """fp64 chain stress=E(F); sim; F=P(F) with the runtime's merged weights (finetune.py:362-364).
+    (dtype = torch.float32: the oracle's own fp32 run, x, v, C, F given in that type)"""
     c = rt.model.constant
     const = om.MPMConstant(int(c.num_grids), float(c.dt), int(c.bound), tuple(float(g) for g in c.gravity), float(c.eps), rt.model.bc)
-    We = [w.detach().cpu().double().requires_grad_(True) for w in rt.elasticity.effective_weights()]
-    Wp = [w.detach().cpu().double().requires_grad_(True) for w in rt.plasticity.effective_weights()]
+    We = [w.detach().cpu().to(dtype).requires_grad_(True) for w in rt.elasticity.effective_weights()]
+    Wp = [w.detach().cpu().to(dtype).requires_grad_(True) for w in rt.plasticity.effective_weights()]
     st = rt.statics
-    vol, rho, clip, en = st.vol.cpu().double(), st.rho.cpu().double(), st.clip_bound.cpu().double(), st.enabled.cpu()
+    vol, rho, clip, en = st.vol.cpu().to(dtype), st.rho.cpu().to(dtype), st.clip_bound.cpu().to(dtype), st.enabled.cpu()
     for _ in range(S):
         stress = omat.elasticity(F, We)
         x, v, C, F = om.step(const, vol, rho, clip, en, x, v, C, F, stress)
         F = omat.plasticity(F, Wp, rt.plasticity.alpha)
     return (x, v, C, F), We, Wp
+
+
+def _lora_factor_grads(rt, dWe, dWp):
+    """dL/dA, dL/dB of the six LoRA layers (elasticity first, A before B: the order of rt.parameters()) from the oracle's
+    gradients of the effective weights: the chain rule through W + s B A, in fp64 (as the test below spells it inline)"""
+    out = []
+    for net, dW in ((rt.elasticity, dWe), (rt.plasticity, dWp)):
+        for lin, d in zip((net.layers[0].fc, net.layers[1].fc, net.final_layer.fc), dW):
+            d = d.double()
+            out.append(lin.scaling * lin.lora_B.detach().cpu().double().T @ d)
+            out.append(lin.scaling * d @ lin.lora_A.detach().cpu().double().T)
+    return out
 
 
 def test_fused_rollout_equals_per_operator_path_and_oracle():
