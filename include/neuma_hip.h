@@ -266,6 +266,74 @@ int nm_mpm_set_field_colliders(nm_mpm* h, int32_t n, const nm_field_collider* ho
 /* rows: DEVICE, (1 + analytic + field colliders) x 9 doubles: walls first, then the colliders in the order they are applied */
 int nm_mpm_contact(nm_mpm* h, double* rows, void* stream);
 
+/* Rigid bodies (no reference counterpart; device code: csrc/nm_rigid.h + the body variants of the collide / contact kernels; the
+ * same definition in fp64: neuma_amd/extras/rigid.py; prose: DESIGN.md section 7 "Rigid bodies").  A rigid body b refers to one
+ * analytic collider of the handle's list by index; it must be a sphere or a box (a plane is refused with a message naming the
+ * entry; field colliders are not in that list at all).  nm_collider keeps its layout.
+ * Constants: mass M > 0; body-frame principal inertia I_b[3] > 0 (sphere: 2/5 M r^2; box with half extents h:
+ *   M/3 (h_y^2 + h_z^2, h_x^2 + h_z^2, h_x^2 + h_y^2); the caller fills them); flags NM_RIGID_NO_GRAVITY (gravity is on by default
+ *   and is the handle's) and NM_RIGID_KINEMATIC (impulses and gravity are ignored and the body keeps v and w: a paddle, a stirrer).
+ * State, fp64, owned by the handle, on the device: centre c[3], unit quaternion q[4] (wxyz; for a box R(q) replaces `rot`),
+ *   linear momentum P[3], angular momentum Lc[3] about the centre in simulation axes.  Initialised from the collider's `center`,
+ *   `rot` (through its quaternion), `velocity` (P = M v) and `angular_velocity` (Lc = R diag(I_b) R^T w).  Derived:
+ *   v = P / M, w = R diag(1 / I_b) R^T Lc (a kinematic body: the `angular_velocity` it was given; its Lc is never touched).
+ * Response: at the grid node at p the collider's own velocity is v_c(p) = v + w x (p - c), evaluated in fp32 from the fp32 copies
+ *   of c, v, w (three more roundings per component than a prescribed collider's constant); nothing else of the sticky / slip /
+ *   friction law changes, and a box's geometry uses the fp32 copy of R(q).
+ * Step (nm_mpm_rigid_step; call it where a prescribed collider would be moved, after the forward and after any nm_mpm_contact):
+ *   reads the grid the last nm_mpm_forward / _ex left, with the poses that forward collided against, takes every body's contact
+ *   row J, L (about the origin) by the launches and the fixed-order fp64 reduction of nm_mpm_contact - which, called between the
+ *   forward and the step, returns the very rows the step consumes -, and in one small kernel (one wave, one lane per body, fp64)
+ *     P  += J + M g dt                                  (g, dt: the handle's fp32 values, widened)
+ *     Lc += L - c x J                                   (the old c)
+ *     c  += (P / M) dt
+ *     q  <- normalize(exp(w dt / 2) (x) q)              the new w with R of the old q; the exact exponential
+ *                                                       (cos(theta/2), sin(theta/2) w / |w|), theta = |w| dt, with
+ *                                                       sin(theta/2)/theta = 1/2 - theta^2/48 + theta^4/3840 for theta < 1e-2
+ *   then refreshes the fp32 pose the collide kernels read.  Nothing is read back, nothing happens on the host.
+ * A handle without bodies launches the kernels it launched before, with the arguments it passed before (their device code is the
+ *   code it was); one with bodies launches k_grid_collide_rigid / k_contact_rows_rigid, whose body entries read c, R, v, w from a
+ *   small wave-uniform device record.  k_contact_rows_rigid visits the active blocks by block id (over the epoch flags), not in the
+ *   order of the active-block list, which differs from run to run: with bodies, nm_mpm_contact's rows - and with them the bodies'
+ *   states - are the same bits in two runs whose grids are.
+ * nm_mpm_grid_export on a handle with bodies collides the blocks no particle touched at the pose the device record holds NOW, while
+ *   the touched blocks hold the velocities the forward collided: the export is consistent between the forward and the step only (a
+ *   prescribed mover has the same property once the caller has moved it).
+ * Forward only: nm_mpm_backward / _ex return NM_ERR_INVALID ("rigid bodies: forward only") on a handle that holds bodies; every
+ *   entry point that refuses colliders refuses bodies with them (a body is a collider).
+ * Out of scope: body-body contact; contact between a body and the box walls or any other collider (a body is moved by the material
+ *   and gravity alone and may leave the cube); mesh colliders as bodies; differentiation.
+ * Stability (documented, not enforced): the coupling is explicit.  For a sticky body the velocity change per substep is
+ *   (sum m_i / M)(u_mean - v), sum m_i the `mass` column of its contact row: it overshoots beyond a ratio of 1 and diverges beyond 2.
+ * nm_mpm_set_colliders on a handle that holds bodies: a list of the SAME length keeps them - the `center`, `rot` and `velocity` of
+ *   a body's entry are ignored (the device record has them), its shape must stay a sphere or a box, its radius / half / surface are
+ *   taken; a list of another length removes the bodies. */
+#define NM_RIGID_KINEMATIC 1
+#define NM_RIGID_NO_GRAVITY 2
+#define NM_RIGID_STATE_COLS 19
+typedef struct nm_rigid_body {
+  int32_t collider;             /* index into the analytic colliders the handle holds now */
+  int32_t flags;                /* NM_RIGID_* */
+  double mass;                  /* M > 0 */
+  double inertia[3];            /* I_b > 0, body frame */
+  double angular_velocity[3];   /* initial w, simulation axes */
+} nm_rigid_body;
+/* Validates and installs `n` bodies (n = 0 removes them), builds their initial state on the host in fp64 and uploads it; it
+ * synchronises the device (a set-up call).  NM_ERR_INVALID with a message "rigid body <q>: <field>: ..." naming the field: a
+ * collider index out of range, an entry that is a plane, the same entry twice (duplicate), unknown flag bits, a non-positive or
+ * non-finite mass or inertia, a non-finite angular_velocity; "rigid bodies: ..." for a null handle / array or n out of range.  A
+ * refused call leaves the handle as it was. */
+int nm_mpm_set_rigid_bodies(nm_mpm* h, int32_t n, const nm_rigid_body* host);
+int32_t nm_mpm_num_rigid_bodies(const nm_mpm* h);
+/* One substep of every body (above).  Asynchronous on `stream`; a no-op on a handle without bodies. */
+int nm_mpm_rigid_step(nm_mpm* h, void* stream);
+/* rows: DEVICE, (1 + analytic + field colliders) x NM_CONTACT_COLS doubles: a copy of the contact rows the last nm_mpm_rigid_step
+ * consumed (nm_mpm_contact's layout; undefined before the first step).  Asynchronous on `stream`; a no-op without bodies. */
+int nm_mpm_rigid_rows(nm_mpm* h, double* rows, void* stream);
+/* out: DEVICE or pinned host memory, n x NM_RIGID_STATE_COLS doubles per body in the order they were set: c[3], q[4], P[3],
+ * Lc[3], v[3], w[3].  Asynchronous on `stream`; a no-op on a handle without bodies. */
+int nm_mpm_rigid_state(nm_mpm* h, double* out, void* stream);
+
 /* Drawing colliders (no reference counterpart; kernels: csrc/nm_draw.hip + csrc/nm_collide_ray.h; the same definition in fp64:
  * neuma_amd/extras/collider_draw.py; prose: DESIGN.md section 7).  Three calls in front of and behind unchanged
  * nm_raster_forward_ex renders; nothing here is differentiated.

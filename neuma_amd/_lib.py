@@ -43,6 +43,11 @@ class nm_collider(C.Structure):
                 ("velocity", C.c_float * 3)]
 
 
+class nm_rigid_body(C.Structure):
+    _fields_ = [("collider", C.c_int32), ("flags", C.c_int32), ("mass", C.c_double), ("inertia", C.c_double * 3),
+                ("angular_velocity", C.c_double * 3)]
+
+
 class nm_field_collider(C.Structure):
     _fields_ = [("surface", C.c_int32), ("friction", C.c_float), ("velocity", C.c_float * 3), ("origin", C.c_float * 3),
                 ("spacing", C.c_float), ("dims", C.c_int32 * 3), ("phi", C.c_void_p)]
@@ -127,6 +132,11 @@ SIGNATURES = {
     "nm_mpm_set_colliders": (C.c_int, [_P, _I32, C.POINTER(nm_collider)]),
     "nm_mpm_set_field_colliders": (C.c_int, [_P, _I32, C.POINTER(nm_field_collider)]),
     "nm_mpm_contact": (C.c_int, [_P, _P, _P]),
+    "nm_mpm_set_rigid_bodies": (C.c_int, [_P, _I32, C.POINTER(nm_rigid_body)]),
+    "nm_mpm_num_rigid_bodies": (_I32, [_P]),
+    "nm_mpm_rigid_step": (C.c_int, [_P, _P]),
+    "nm_mpm_rigid_state": (C.c_int, [_P, _P, _P]),
+    "nm_mpm_rigid_rows": (C.c_int, [_P, _P, _P]),
     "nm_collider_cast": (C.c_int, [C.POINTER(nm_raster_cfg), C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_float), _I32,
                                   C.POINTER(nm_collider), C.POINTER(nm_collider_style), _P, _P, _P, _P]),
     "nm_collider_hide": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), _I32, C.POINTER(nm_collider), _I32,

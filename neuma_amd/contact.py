@@ -8,11 +8,11 @@ restatement: neuma_amd/extras/contact.py; kernels: csrc/nm_contact.h + k_contact
     meter.write_csv(path); print(meter.summary())
 
 record() keeps the substep's rows on the device together with the torque impulse about each obstacle's reference point AS IT IS
-THEN - the plane's point, the centre of a sphere or box, the lattice centre of a field collider, the simulation origin for the
-walls - which is why it comes before step_colliders().  frame() sums the substeps since the last frame and divides by the
-simulated time they cover: F = sum J / T, torque = sum (L - r0 x J) / T, normal = sum N / T (the mean normal force); mass and nodes are
-means over the frame's substeps.  Nothing is read back to the host before write_csv() / summary().  Simulation units throughout
-(the unit cube, rho * vol masses): no conversion to world units.
+THEN - the plane's point, the centre of a sphere or box (a rigid body's: its centre on the device at that substep), the lattice
+centre of a field collider, the simulation origin for the walls - which is why it comes before step_colliders().  frame() sums the
+substeps since the last frame and divides by the simulated time they cover: F = sum J / T, torque = sum (L - r0 x J) / T, normal =
+sum N / T (the mean normal force); mass and nodes are means over the frame's substeps. Nothing is read back to the host before
+write_csv() / summary(). Simulation units throughout (the unit cube, rho * vol masses): no conversion to world units.
 
 `--report_contacts` on `python -m neuma_amd.render` / `python -m neuma_amd.inference` (or `sim.report_contacts: true`) runs a
 meter with one substep per frame and writes <result dir>/contacts_<video_name>.csv.
@@ -38,10 +38,22 @@ def reference_points(model) -> List[tuple]:
     """One torque reference per row of model.contact(), where the obstacles are NOW: the origin for the walls, a plane's point, the
     centre of a sphere or box, the centre of a field collider's lattice."""
     pts = [(0.0, 0.0, 0.0)]
-    for c in model.colliders:
+    # (with rigid bodies: the list the host holds, without a read-back - a body's entry is where it started, and reference_tensor
+    #  puts its centre in.  getattr: the meter also serves stand-ins of a model that have `colliders` and nothing newer)
+    for c in (model.prescribed_colliders if getattr(model, "rigid_bodies", None) else model.colliders):
         pts.append(tuple(c.point if isinstance(c, Plane) else c.center))
     for c in model.field_colliders:
         pts.append(tuple(o + 0.5 * (d - 1) * c.spacing for o, d in zip(c.origin, c.dims)))
+    return pts
+
+
+def reference_tensor(model, like: torch.Tensor) -> torch.Tensor:
+    """reference_points as an (R, 3) tensor like `like`, the rows of rigid bodies taken from the centres of model.rigid_state() on
+    the device: nothing is read back"""
+    pts = torch.as_tensor(reference_points(model), dtype=like.dtype, device=like.device)
+    bodies = model.rigid_bodies
+    if bodies:
+        pts[torch.as_tensor([1 + i for i, _ in bodies], device=like.device)] = model.rigid_state()[:, 0:3].to(like.dtype)
     return pts
 
 
@@ -66,7 +78,8 @@ class ContactMeter(object):
         rep = self.model.contact() if report is None else report
         if self.names is None:
             self.names = list(rep.names)
-        self._open.append((rep.rows, shifted(rep.angular, rep.impulse, reference_points(self.model))))
+        about = reference_tensor(self.model, rep.rows) if getattr(self.model, "rigid_bodies", None) else reference_points(self.model)
+        self._open.append((rep.rows, shifted(rep.angular, rep.impulse, about)))
         return rep
 
     def frame(self) -> ContactReport:

@@ -13,9 +13,11 @@
 // columns of a row: J[3], L[3], N, mass, nodes (NM_CONTACT_COLS of neuma_hip.h)
 #define NM_CONTACT_N NM_CONTACT_COLS
 
-// a: the node's {mv, m}; row is wave-uniform.  Nodes without mass carry no momentum and add nothing.
-__device__ __forceinline__ void contact_node(const MpmK& K, const ColliderSet& A, const FieldColliderSet& F, int row, int i, int j,
-                                             int k, const float4& a, double acc[NM_CONTACT_N]) {
+// a: the node's {mv, m}; row is wave-uniform.  Nodes without mass carry no momentum and add nothing.  BODIES: entries of A that the
+// view B marks take pose and velocity field from its record (nm_collide.h); false never looks at B.
+template <bool BODIES>
+__device__ __forceinline__ void contact_node(const MpmK& K, const ColliderSet& A, const RigidView& B, const FieldColliderSet& F, int row,
+                                             int i, int j, int k, const float4& a, double acc[NM_CONTACT_N]) {
   if (!(a.w > 0.f)) return;
   float u[3], mk[3];
   grid_velocity(K, i, j, k, a, u, mk);
@@ -30,11 +32,11 @@ __device__ __forceinline__ void contact_node(const MpmK& K, const ColliderSet& A
     const int c = row - 1;
     u[0] = un[0]; u[1] = un[1]; u[2] = un[2];
     const int na = c < A.n ? c : A.n;
-    for (int e = 0; e < na; ++e) collide_apply(A.c[e], p, u);
+    for (int e = 0; e < na; ++e) collide_apply_entry<BODIES>(A, B, e, p, u);
     if (c < A.n) {
       un[0] = u[0]; un[1] = u[1]; un[2] = u[2];
-      inside = collide_apply(A.c[c], p, un);
-      if (inside) collide_normal(A.c[c], p, n);
+      inside = collide_apply_entry<BODIES>(A, B, c, p, un);
+      if (inside) collide_normal_entry<BODIES>(A, B, c, p, n);
     } else {
       const int f = c - A.n;
       for (int e = 0; e < f; ++e) field_apply(F.c[e], p, u);

@@ -21,6 +21,7 @@
 #include "nm_collide.h"
 #include "nm_collide_field.h"
 #include "nm_contact.h"
+#include "nm_rigid.h"
 #include "nm_reduce.h"
 #include <stdlib.h>
 #include <string.h>
@@ -57,7 +58,13 @@ struct nm_mpm {
   ColliderSet colliders;   // nm_mpm_set_colliders (host copy; travels by value in the arguments of the collider kernels)
   FieldColliderSet fields; // nm_mpm_set_field_colliders (likewise; the phi arrays stay the caller's)
   double* contact_ws;      // nm_mpm_contact: per-workgroup partial rows, allocated on first use
+  int n_bodies;            // nm_mpm_set_rigid_bodies: rigid bodies among the analytic colliders (nm_rigid.h); 0 = none, and then ...
+  unsigned body_mask;      // ... (bit c: collider c is a body) every launch below is the one a handle without bodies makes
+  RigidBody* bodies;       // device: constants and fp64 state, [NM_MAX_COLLIDERS], allocated with the first body
+  RigidPose* body_pose;    // device: the fp32 pose the collide kernels read, indexed by collider
+  double* body_rows;       // device: the contact rows nm_mpm_rigid_step consumes
 };
+static RigidView rigid_view(const nm_mpm* h) { return RigidView{h->body_mask, h->body_pose}; }
 int nm_mpm_num_colliders(const nm_mpm* h) { return h->colliders.n + h->fields.n; }      // analytic and field colliders alike
 void nm_mpm_set_fresh_rows(nm_mpm* h, int on) { h->fresh_rows = on; }
 
@@ -1076,6 +1083,26 @@ __global__ void __launch_bounds__(256) k_grid_collide(const int* __restrict__ li
     if (hit) gv[node] = make_float4(u[0], u[1], u[2], q.w);
   }
 }
+// the same sweep for a handle that holds rigid bodies (nm_collide.h): their entries take pose and velocity field from the device
+// record B.pose, the others stay what they are
+__global__ void __launch_bounds__(256) k_grid_collide_rigid(const int* __restrict__ list, const int* __restrict__ count,
+                                                            float4* __restrict__ gv, MpmK K, ColliderSet S, RigidView B) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int cnt = *count;
+  for (int li = blockIdx.x * 4 + wave; li < cnt; li += gridDim.x * 4) {
+    const int b = list[li];
+    int i, j, k;
+    block_coords(b, K.nb, lane, i, j, k);
+    if (!(i < K.G && j < K.G && k < K.G)) continue;      // padding nodes: velocity defined as zero
+    const int node = (b << 6) + lane;
+    const float p[3] = {(float)i * K.dx, (float)j * K.dx, (float)k * K.dx};
+    float4 q = gv[node];
+    float u[3] = {q.x, q.y, q.z};
+    bool hit = false;
+    for (int c = 0; c < S.n; ++c) hit = collide_apply_entry<true>(S, B, c, p, u) || hit;
+    if (hit) gv[node] = make_float4(u[0], u[1], u[2], q.w);
+  }
+}
 
 // adjoint of k_grid_collide, in front of k_grid_op_bwd: gg {dL/du'} -> {dL/du}, u the velocity behind the box boundary
 // condition.  u is recomputed from {mv, m} through grid_velocity and the transposed Jacobians are applied in reverse order.
@@ -1437,6 +1464,29 @@ __global__ void k_grid_export(MpmK K, const float4* __restrict__ gm, const float
   if (m) m[t] = q.w;
   if (v) { v[3 * t] = u.x; v[3 * t + 1] = u.y; v[3 * t + 2] = u.z; }
 }
+// k_grid_export for a handle that holds rigid bodies: the untouched blocks are collided at the bodies' poses too
+__global__ void k_grid_export_rigid(MpmK K, const float4* __restrict__ gm, const float4* __restrict__ gv, float* mv, float* m,
+                                    float* v, const int* __restrict__ flags, int epoch, ColliderSet S, RigidView B, FieldColliderSet F) {
+  int t = blockIdx.x * blockDim.x + threadIdx.x;
+  int G = K.G;
+  if (t >= G * G * G) return;
+  int i = t / (G * G), r = t - i * G * G, j = r / G, k = r - j * G;
+  int a = node_addr(i, j, k, K.nb);
+  float4 q = gm[a], u = gv[a];
+  if (flags[((i >> 2) * K.nb + (j >> 2)) * K.nb + (k >> 2)] != epoch) {
+    q = make_float4(0.f, 0.f, 0.f, 0.f);
+    float w[3], mk[3];
+    grid_velocity(K, i, j, k, q, w, mk);
+    w[0] *= mk[0]; w[1] *= mk[1]; w[2] *= mk[2];
+    const float p[3] = {(float)i * K.dx, (float)j * K.dx, (float)k * K.dx};
+    for (int c = 0; c < S.n; ++c) collide_apply_entry<true>(S, B, c, p, w);      // (the dense sweep would have visited this node too)
+    for (int c = 0; c < F.n; ++c) field_apply(F.c[c], p, w);
+    u = make_float4(w[0], w[1], w[2], 0.f);
+  }
+  if (mv) { mv[3 * t] = q.x; mv[3 * t + 1] = q.y; mv[3 * t + 2] = q.z; }
+  if (m) m[t] = q.w;
+  if (v) { v[3 * t] = u.x; v[3 * t + 1] = u.y; v[3 * t + 2] = u.z; }
+}
 
 // Contact report (nm_contact.h; definition: include/neuma_hip.h "Contact report"): the sweep of k_grid_collide - one wave per
 // active block, one lane per node, padding nodes skipped - read-only over {mv, m}.  blockIdx.y is the row: each lane keeps the
@@ -1458,7 +1508,29 @@ __global__ void __launch_bounds__(256) k_contact_rows(const int* __restrict__ li
     int i, j, k;
     block_coords(b, K.nb, lane, i, j, k);
     if (!(i < K.G && j < K.G && k < K.G)) continue;      // padding nodes: velocity defined as zero, no collider acts on them
-    contact_node(K, A, F, row, i, j, k, gm[(b << 6) + lane], acc);
+    contact_node<false>(K, A, RigidView{0u, nullptr}, F, row, i, j, k, gm[(b << 6) + lane], acc);
+  }
+  const auto tot = nm_block_reduce<4, NmSum>(acc, sh);
+  if (threadIdx.x < NM_CONTACT_N) part[((size_t)row * gridDim.x + blockIdx.x) * NM_CONTACT_N + threadIdx.x] = tot[threadIdx.x];
+}
+// k_contact_rows for a handle that holds rigid bodies.  Its rows move the bodies, so two runs of one scene must sum them in one
+// order: the active blocks are visited by block id over the epoch flags - which name the blocks of the list - and not by the list,
+// whose order is whatever order the scatter's threads appended in.  A body's state is then repeatable to the bit wherever the grid is.
+__global__ void __launch_bounds__(256) k_contact_rows_rigid(const int* __restrict__ flags, int epoch, int nblocks,
+                                                            const float4* __restrict__ gm, MpmK K, ColliderSet A, RigidView B,
+                                                            FieldColliderSet F, double* __restrict__ part) {
+  __shared__ double sh[4 * NM_CONTACT_N];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = blockIdx.y;
+  double acc[NM_CONTACT_N];
+#pragma unroll
+  for (int q = 0; q < NM_CONTACT_N; ++q) acc[q] = 0.0;
+  for (int b = blockIdx.x * 4 + wave; b < nblocks; b += gridDim.x * 4) {
+    if (flags[b] != epoch) continue;      // (wave-uniform)
+    int i, j, k;
+    block_coords(b, K.nb, lane, i, j, k);
+    if (!(i < K.G && j < K.G && k < K.G)) continue;      // padding nodes: velocity defined as zero, no collider acts on them
+    contact_node<true>(K, A, B, F, row, i, j, k, gm[(b << 6) + lane], acc);
   }
   const auto tot = nm_block_reduce<4, NmSum>(acc, sh);
   if (threadIdx.x < NM_CONTACT_N) part[((size_t)row * gridDim.x + blockIdx.x) * NM_CONTACT_N + threadIdx.x] = tot[threadIdx.x];
@@ -1522,6 +1594,8 @@ extern "C" int nm_mpm_create(const nm_mpm_cfg* cfg, nm_mpm** out) {
   h->colliders.n = 0;
   h->fields.n = 0;
   h->contact_ws = nullptr;
+  h->n_bodies = 0; h->body_mask = 0u;
+  h->bodies = nullptr; h->body_pose = nullptr; h->body_rows = nullptr;
   *out = h;
   return NM_OK;
 }
@@ -1537,6 +1611,7 @@ extern "C" int nm_mpm_destroy(nm_mpm* h) {
   if (h->sh_slot) hipFree(h->sh_slot);
   if (h->sh_dil) hipFree(h->sh_dil);
   if (h->contact_ws) hipFree(h->contact_ws);
+  if (h->bodies) { hipFree(h->bodies); hipFree(h->body_pose); hipFree(h->body_rows); }
   delete h;
   return NM_OK;
 }
@@ -1616,7 +1691,11 @@ static int launch_grid_op(nm_mpm* h, void* save, int cap, const int* skip, int32
 // launched when the handle holds none of its kind
 static int launch_grid_collide(nm_mpm* h, hipStream_t s) {
   const int now = h->cur;
-  if (h->colliders.n != 0) {
+  if (h->n_bodies != 0) {      // (bodies are analytic entries: the set is not empty)
+    NM_LAUNCH(k_grid_collide_rigid, dim3(kSweepGrid), dim3(256), 0, s, (const int*)h->list[now], (const int*)(h->count + now), h->gv,
+                       h->k, h->colliders, rigid_view(h));
+    NM_LAUNCH_CHECK();
+  } else if (h->colliders.n != 0) {
     NM_LAUNCH(k_grid_collide, dim3(kSweepGrid), dim3(256), 0, s, (const int*)h->list[now], (const int*)(h->count + now), h->gv, h->k,
                        h->colliders);
     NM_LAUNCH_CHECK();
@@ -1864,6 +1943,7 @@ int nm_mpm_backward_cached_finish(nm_mpm* h, int32_t n, const nm_statics* st, co
 extern "C" int nm_mpm_backward_ex(nm_mpm* h, int32_t n, const nm_statics* st, const nm_particles* cur,
                                   const nm_particles* next, const nm_particles* gnext, nm_particles* gcur,
                                   const void* gridrec, int32_t cap_blocks, void* stream) {
+  NM_REQUIRE(!h || h->n_bodies == 0, "rigid bodies: forward only");
   if (n == 0) return NM_OK;
   int rc = nm_mpm_backward_cached_begin(h, n, st, cur, next, gnext, gcur, gridrec, cap_blocks, false, false, stream);
   if (rc) return rc;
@@ -2034,10 +2114,101 @@ extern "C" int nm_mpm_set_colliders(nm_mpm* h, int32_t n, const nm_collider* hos
       NM_REQUIREF(det > 0.0, "collider %d: rot: not orthonormal (a reflection: determinant -1)", q);
     }
   }
+  // a handle that holds rigid bodies: a list of the same length keeps them (the host pose of their entries is ignored: the
+  // device record has it), provided every body's entry is still a sphere or box; a list of another length removes them
+  if (h->n_bodies != 0 && n == h->colliders.n) {
+    for (int q = 0; q < n; ++q)
+      NM_REQUIREF(!((h->body_mask >> q) & 1u) || host[q].shape == NM_COLLIDER_SPHERE || host[q].shape == NM_COLLIDER_BOX,
+                  "collider %d: shape: the entry is a rigid body and must stay a sphere or a box", q);
+  } else {
+    h->n_bodies = 0; h->body_mask = 0u;
+  }
   h->colliders.n = n;
   for (int q = 0; q < n; ++q) h->colliders.c[q] = host[q];
   return NM_OK;
 }
+
+// ---- rigid bodies: validation, the initial state (host, fp64) and its upload
+static bool finite3d(const double* v) { return fabs(v[0]) <= 1.7976931348623157e308 && fabs(v[1]) <= 1.7976931348623157e308 && fabs(v[2]) <= 1.7976931348623157e308; }
+// unit quaternion (w, x, y, z) of a rotation matrix (row-major), by the largest of the four squared components
+static void rot_to_quat(const double R[9], double q[4]) {
+  const double tr = R[0] + R[4] + R[8];
+  if (tr > 0.0) {
+    const double s = 2.0 * sqrt(1.0 + tr);
+    q[0] = 0.25 * s; q[1] = (R[7] - R[5]) / s; q[2] = (R[2] - R[6]) / s; q[3] = (R[3] - R[1]) / s;
+  } else if (R[0] > R[4] && R[0] > R[8]) {
+    const double s = 2.0 * sqrt(1.0 + R[0] - R[4] - R[8]);
+    q[0] = (R[7] - R[5]) / s; q[1] = 0.25 * s; q[2] = (R[1] + R[3]) / s; q[3] = (R[2] + R[6]) / s;
+  } else if (R[4] > R[8]) {
+    const double s = 2.0 * sqrt(1.0 + R[4] - R[0] - R[8]);
+    q[0] = (R[2] - R[6]) / s; q[1] = (R[1] + R[3]) / s; q[2] = 0.25 * s; q[3] = (R[5] + R[7]) / s;
+  } else {
+    const double s = 2.0 * sqrt(1.0 + R[8] - R[0] - R[4]);
+    q[0] = (R[3] - R[1]) / s; q[1] = (R[2] + R[6]) / s; q[2] = (R[5] + R[7]) / s; q[3] = 0.25 * s;
+  }
+  const double inv = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  for (int a = 0; a < 4; ++a) q[a] *= inv;
+}
+extern "C" int nm_mpm_set_rigid_bodies(nm_mpm* h, int32_t n, const nm_rigid_body* host) {
+  NM_REQUIRE(h, "rigid bodies: null handle");
+  NM_REQUIREF(n >= 0 && n <= NM_MAX_COLLIDERS, "rigid bodies: n = %d outside 0..%d", n, NM_MAX_COLLIDERS);
+  NM_REQUIRE(n == 0 || host, "rigid bodies: null array");
+  unsigned mask = 0u;
+  for (int q = 0; q < n; ++q) {
+    const nm_rigid_body& b = host[q];
+    NM_REQUIREF(b.collider >= 0 && b.collider < h->colliders.n, "rigid body %d: collider: index %d outside the %d analytic colliders", q,
+                b.collider, h->colliders.n);
+    const int shape = h->colliders.c[b.collider].shape;
+    NM_REQUIREF(shape == NM_COLLIDER_SPHERE || shape == NM_COLLIDER_BOX,
+                "rigid body %d: collider: entry %d is a plane (only a sphere or a box can be a rigid body)", q, b.collider);
+    NM_REQUIREF(!((mask >> b.collider) & 1u), "rigid body %d: collider: entry %d is a rigid body already (duplicate)", q, b.collider);
+    NM_REQUIREF((b.flags & ~(NM_RIGID_KINEMATIC | NM_RIGID_NO_GRAVITY)) == 0, "rigid body %d: flags: unknown flag bits %d", q, b.flags);
+    NM_REQUIREF(b.mass > 0.0 && b.mass <= 1.7976931348623157e308, "rigid body %d: mass: must be positive and finite", q);
+    NM_REQUIREF(b.inertia[0] > 0.0 && b.inertia[1] > 0.0 && b.inertia[2] > 0.0 && finite3d(b.inertia),
+                "rigid body %d: inertia: three positive finite numbers expected", q);
+    NM_REQUIREF(finite3d(b.angular_velocity), "rigid body %d: angular_velocity: three finite numbers expected", q);
+    mask |= 1u << b.collider;
+  }
+  if (n == 0) {
+    h->n_bodies = 0; h->body_mask = 0u;
+    return NM_OK;
+  }
+  if (!h->bodies) {
+    NM_HIP_CHECK(hipMalloc(&h->bodies, NM_MAX_COLLIDERS * sizeof(RigidBody)));
+    NM_HIP_CHECK(hipMalloc(&h->body_pose, NM_MAX_COLLIDERS * sizeof(RigidPose)));
+    NM_HIP_CHECK(hipMalloc(&h->body_rows, (1 + NM_MAX_COLLIDERS + NM_MAX_FIELD_COLLIDERS) * NM_CONTACT_N * sizeof(double)));
+  }
+  RigidBody init[NM_MAX_COLLIDERS];
+  RigidPose pose[NM_MAX_COLLIDERS];
+  memset(init, 0, sizeof(init));
+  memset(pose, 0, sizeof(pose));
+  for (int q = 0; q < n; ++q) {
+    const nm_rigid_body& b = host[q];
+    const nm_collider& c = h->colliders.c[b.collider];
+    RigidBody& o = init[q];
+    double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    if (c.shape == NM_COLLIDER_BOX)
+      for (int a = 0; a < 9; ++a) R[a] = (double)c.rot[a];
+    rot_to_quat(R, o.q);
+    rigid_rot(o.q, R);      // (the rotation the state holds from here on)
+    o.mass = b.mass; o.collider = b.collider; o.flags = b.flags;
+    for (int a = 0; a < 3; ++a) {
+      o.c[a] = (double)c.center[a];
+      o.P[a] = b.mass * (double)c.velocity[a];
+      o.inertia[a] = b.inertia[a];
+      o.w_kin[a] = b.angular_velocity[a];
+    }
+    rigid_momentum(R, o.inertia, b.angular_velocity, o.Lc);
+    rigid_pose(o, pose);
+  }
+  NM_HIP_CHECK(hipDeviceSynchronize());      // (a substep in flight may still read the records)
+  NM_HIP_CHECK(hipMemcpy(h->bodies, init, sizeof(init), hipMemcpyHostToDevice));
+  NM_HIP_CHECK(hipMemcpy(h->body_pose, pose, sizeof(pose), hipMemcpyHostToDevice));
+  NM_HIP_CHECK(hipDeviceSynchronize());
+  h->n_bodies = n; h->body_mask = mask;
+  return NM_OK;
+}
+int32_t nm_mpm_num_rigid_bodies(const nm_mpm* h) { return h ? h->n_bodies : 0; }
 
 // ---- field colliders: the same, for obstacles given as a signed distance field (the phi arrays stay the caller's)
 extern "C" int nm_mpm_set_field_colliders(nm_mpm* h, int32_t n, const nm_field_collider* host) {
@@ -2082,8 +2253,31 @@ extern "C" int nm_mpm_grid_stats(nm_mpm* h, int32_t* active_blocks, int32_t* nod
 extern "C" int nm_mpm_grid_export(nm_mpm* h, float* mv, float* m, float* v, void* stream) {
   NM_REQUIRE(h, "null handle");
   int G = h->k.G;
-  NM_LAUNCH(k_grid_export, dim3(nm_div_up((int64_t)G * G * G, 256)), dim3(256), 0, (hipStream_t)stream, h->k,
-                     h->gm, h->gv, mv, m, v, h->flags, h->epoch, h->colliders, h->fields);
+  if (h->n_bodies != 0) {
+    NM_LAUNCH(k_grid_export_rigid, dim3(nm_div_up((int64_t)G * G * G, 256)), dim3(256), 0, (hipStream_t)stream, h->k, h->gm, h->gv, mv,
+                       m, v, h->flags, h->epoch, h->colliders, rigid_view(h), h->fields);
+  } else {
+    NM_LAUNCH(k_grid_export, dim3(nm_div_up((int64_t)G * G * G, 256)), dim3(256), 0, (hipStream_t)stream, h->k,
+                       h->gm, h->gv, mv, m, v, h->flags, h->epoch, h->colliders, h->fields);
+  }
+  NM_LAUNCH_CHECK();
+  return NM_OK;
+}
+
+// the contact rows of the last forward into `rows` (device): the launches of nm_mpm_contact and of nm_mpm_rigid_step alike
+static int launch_contact(nm_mpm* h, double* rows, hipStream_t s) {
+  const int max_rows = 1 + NM_MAX_COLLIDERS + NM_MAX_FIELD_COLLIDERS;
+  if (!h->contact_ws) NM_HIP_CHECK(hipMalloc(&h->contact_ws, (size_t)max_rows * kSweepGrid * NM_CONTACT_N * sizeof(double)));
+  const int nrows = 1 + h->colliders.n + h->fields.n;
+  if (h->n_bodies != 0) {
+    NM_LAUNCH(k_contact_rows_rigid, dim3(kSweepGrid, nrows), dim3(256), 0, s, (const int*)h->flags, h->epoch, h->nblocks,
+                       (const float4*)h->gm, h->k, h->colliders, rigid_view(h), h->fields, h->contact_ws);
+  } else {
+    NM_LAUNCH(k_contact_rows, dim3(kSweepGrid, nrows), dim3(256), 0, s, (const int*)h->list[h->cur], (const int*)(h->count + h->cur),
+                       (const float4*)h->gm, h->k, h->colliders, h->fields, h->contact_ws);
+  }
+  NM_LAUNCH_CHECK();
+  NM_LAUNCH(k_contact_sum, dim3(nrows), dim3(256), 0, s, (const double*)h->contact_ws, kSweepGrid, rows);
   NM_LAUNCH_CHECK();
   return NM_OK;
 }
@@ -2091,14 +2285,36 @@ extern "C" int nm_mpm_grid_export(nm_mpm* h, float* mv, float* m, float* v, void
 extern "C" int nm_mpm_contact(nm_mpm* h, double* rows, void* stream) {
   NM_REQUIRE(h, "contact: null handle");
   NM_REQUIRE(rows, "contact: null rows");
+  return launch_contact(h, rows, (hipStream_t)stream);
+}
+
+extern "C" int nm_mpm_rigid_step(nm_mpm* h, void* stream) {
+  NM_REQUIRE(h, "rigid bodies: null handle");
+  if (h->n_bodies == 0) return NM_OK;
   hipStream_t s = (hipStream_t)stream;
-  const int max_rows = 1 + NM_MAX_COLLIDERS + NM_MAX_FIELD_COLLIDERS;
-  if (!h->contact_ws) NM_HIP_CHECK(hipMalloc(&h->contact_ws, (size_t)max_rows * kSweepGrid * NM_CONTACT_N * sizeof(double)));
-  const int nrows = 1 + h->colliders.n + h->fields.n;
-  NM_LAUNCH(k_contact_rows, dim3(kSweepGrid, nrows), dim3(256), 0, s, (const int*)h->list[h->cur], (const int*)(h->count + h->cur),
-                     (const float4*)h->gm, h->k, h->colliders, h->fields, h->contact_ws);
+  int rc = launch_contact(h, h->body_rows, s);
+  if (rc) return rc;
+  const double dt = (double)h->cfg.dt;
+  NM_LAUNCH(k_rigid_step, dim3(1), dim3(64), 0, s, h->bodies, h->n_bodies, (const double*)h->body_rows, (double)h->cfg.gravity[0],
+                     (double)h->cfg.gravity[1], (double)h->cfg.gravity[2], dt, h->body_pose);
   NM_LAUNCH_CHECK();
-  NM_LAUNCH(k_contact_sum, dim3(nrows), dim3(256), 0, s, (const double*)h->contact_ws, kSweepGrid, rows);
+  return NM_OK;
+}
+
+extern "C" int nm_mpm_rigid_rows(nm_mpm* h, double* rows, void* stream) {
+  NM_REQUIRE(h, "rigid bodies: null handle");
+  if (h->n_bodies == 0) return NM_OK;
+  NM_REQUIRE(rows, "rigid bodies: null rows");
+  const size_t nrows = 1 + h->colliders.n + h->fields.n;
+  NM_HIP_CHECK(hipMemcpyAsync(rows, h->body_rows, nrows * NM_CONTACT_N * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return NM_OK;
+}
+
+extern "C" int nm_mpm_rigid_state(nm_mpm* h, double* out, void* stream) {
+  NM_REQUIRE(h, "rigid bodies: null handle");
+  if (h->n_bodies == 0) return NM_OK;
+  NM_REQUIRE(out, "rigid bodies: null out");
+  NM_LAUNCH(k_rigid_state, dim3(1), dim3(64), 0, (hipStream_t)stream, (const RigidBody*)h->bodies, h->n_bodies, out);
   NM_LAUNCH_CHECK();
   return NM_OK;
 }

@@ -107,20 +107,28 @@ def apply_field_collider(c: FieldCollider, p: Tensor, u: Tensor) -> Tensor:
     return _respond(c, inside, n, u)
 
 
-def apply_collider(c, p: Tensor, u: Tensor) -> Tensor:
-    """One collider's response at the nodes p (M, 3) with velocities u (M, 3)."""
+def apply_collider(c, p: Tensor, u: Tensor, omega=None) -> Tensor:
+    """One collider's response at the nodes p (M, 3) with velocities u (M, 3).  omega (3,): the collider is a rigid body (a Sphere
+    or Box at its current pose, extras/rigid.py posed) that turns about its centre, and its own velocity at a node is
+    velocity + omega x (p - center); None: the constant `velocity`."""
     if isinstance(c, FieldCollider):
         return apply_field_collider(c, p, u)
     with torch.no_grad():
         sdf, n = sdf_normal(c, p.to(u.dtype))
         inside = sdf < 0
-    return _respond(c, inside, n, u)
+    if omega is None:
+        return _respond(c, inside, n, u)
+    w = torch.as_tensor(omega, dtype=u.dtype).reshape(3).expand_as(u)
+    d = p.to(u.dtype) - torch.as_tensor(c.center, dtype=u.dtype)
+    return _respond(c, inside, n, u, torch.as_tensor(c.velocity, dtype=u.dtype) + torch.linalg.cross(w, d))
 
 
-def _respond(c, inside: Tensor, n: Tensor, u: Tensor) -> Tensor:
-    """The sticky / slip / friction law at the nodes `inside`, given the outward normals n."""
+def _respond(c, inside: Tensor, n: Tensor, u: Tensor, vc=None) -> Tensor:
+    """The sticky / slip / friction law at the nodes `inside`, given the outward normals n (vc: the collider's own velocity per
+    node, if it is not the constant c.velocity)."""
     dt = u.dtype
-    vc = torch.as_tensor(c.velocity, dtype=dt).expand_as(u)
+    if vc is None:
+        vc = torch.as_tensor(c.velocity, dtype=dt).expand_as(u)
     if c.surface == "sticky":
         new = vc
     else:
@@ -141,12 +149,13 @@ def _respond(c, inside: Tensor, n: Tensor, u: Tensor) -> Tensor:
     return torch.where(inside[:, None], new, u)
 
 
-def apply_colliders(colliders: Sequence, u: Tensor, num_grids: int) -> Tensor:
-    """u (G^3, 3) or (G, G, G, 3): node velocities behind the box boundary condition -> behind the colliders, in list order."""
+def apply_colliders(colliders: Sequence, u: Tensor, num_grids: int, omegas: Sequence = ()) -> Tensor:
+    """u (G^3, 3) or (G, G, G, 3): node velocities behind the box boundary condition -> behind the colliders, in list order.
+    omegas: one entry per collider (None for one that does not turn), or empty."""
     G = int(num_grids)
     shape = u.shape
     out = u.reshape(G * G * G, 3)
     p = node_positions(G, out.dtype)
-    for c in colliders:
-        out = apply_collider(c, p, out)
+    for i, c in enumerate(colliders):
+        out = apply_collider(c, p, out) if not omegas or omegas[i] is None else apply_collider(c, p, out, omegas[i])
     return out.reshape(shape)

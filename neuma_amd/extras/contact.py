@@ -18,6 +18,9 @@ Row r (0: the box walls, r >= 1: collider r) is the impulse the body hands to ob
     mass   sum_inside m                                walls: the boundary layers (an index < bound or >= G - bound on any axis)
     nodes  the number of those nodes
 
+A collider that is a rigid body (extras/rigid.py) goes in at its current pose (rigid.posed) with its angular velocity in
+`omegas`, one entry per collider (None for the others): its own velocity at a node is then v + w x (p - c).
+
 `scale` (R,) is S_r = sum_inside m (|u^(r)| + |u^(r+1)|), what a parity test divides an error of row r by.  Everything is fp64.
 Units are simulation units (the unit cube, rho * vol masses).  force() / torque() derive F = J / dt and (L - r0 x J) / dt.
 Not on the product path: nothing here is called by a simulation, and nothing here imports the test oracle.
@@ -70,7 +73,7 @@ def collider_inside_normal(c, p: Tensor) -> Tuple[Tensor, Tensor]:
 
 
 def contact_chain(mv: Tensor, m: Tensor, *, dt: float, gravity, eps: float, bound: int, bc: str, num_grids: int,
-                  colliders: Sequence = ()):
+                  colliders: Sequence = (), omegas: Sequence = ()):
     """[u^(0), u^(1), ..., u^(R)] (each (G^3, 3) fp64; R = 1 + len(colliders)): the velocities along the chain at EVERY node."""
     G = int(num_grids)
     mv = torch.as_tensor(mv).detach().cpu().double().reshape(G ** 3, 3)
@@ -78,17 +81,19 @@ def contact_chain(mv: Tensor, m: Tensor, *, dt: float, gravity, eps: float, boun
     p = xc.node_positions(G)
     chain = [free_velocity(mv, m, float(dt), gravity, float(eps))]
     chain.append(box_bc(chain[0], G, int(bound), bc))
-    for c in colliders:
-        chain.append(xc.apply_collider(c, p, chain[-1]))
+    for i, c in enumerate(colliders):
+        chain.append(xc.apply_collider(c, p, chain[-1]) if not omegas or omegas[i] is None
+                     else xc.apply_collider(c, p, chain[-1], omegas[i]))
     return chain
 
 
 def contact_rows(mv: Tensor, m: Tensor, *, dt: float, gravity, eps: float, bound: int, bc: str, num_grids: int,
-                 colliders: Sequence = ()) -> Tuple[Tensor, Tensor]:
+                 colliders: Sequence = (), omegas: Sequence = ()) -> Tuple[Tensor, Tensor]:
     """(rows (R, 9) fp64, scale (R,) fp64), R = 1 + len(colliders): see the module docstring."""
     G = int(num_grids)
     m = torch.as_tensor(m).detach().cpu().double().reshape(G ** 3)
-    chain = contact_chain(mv, m, dt=dt, gravity=gravity, eps=eps, bound=bound, bc=bc, num_grids=G, colliders=colliders)
+    chain = contact_chain(mv, m, dt=dt, gravity=gravity, eps=eps, bound=bound, bc=bc, num_grids=G, colliders=colliders,
+                          omegas=omegas)
     p = xc.node_positions(G)
     has = m > 0
     mm = torch.where(has, m, torch.zeros_like(m))

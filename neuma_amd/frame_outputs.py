@@ -18,6 +18,8 @@ and the writers.  The products (only the images and the particle files have a re
                        former): the colliders of `sim.colliders` in every image (collider_draw.py)
     contacts           --report_contacts (`sim.report_contacts`): force and torque on the box walls and on each collider per frame
                        -> contacts_<video_name>.csv and a summary at the end (contact.py; simulation units)
+    rigid bodies       a `sim.colliders` entry with `dynamic: true` / `kinematic: true`: pose and velocities of every body per frame
+                       -> rigid_<video_name>.csv, always, and a note per body whose contact mass exceeded its own (rigid.py)
     driven meshes      `drive_mesh`: a user's triangle mesh carried by an object's particles -> driven_<name>/ (mesh_drive.py)
 
 `output_paths` says where each goes.  Render numbers images and products first_step + step, inference numbers them step; the
@@ -27,7 +29,7 @@ from typing import Dict, Optional, Sequence
 
 import torch
 
-from . import collider_draw, contact, field_paint, io as nio
+from . import collider_draw, contact, field_paint, io as nio, rigid
 from .sim.colliders import describe as describe_colliders, describe_fields as describe_field_colliders
 from .tune import denormalize_points_helper_func
 
@@ -126,7 +128,7 @@ class FrameWriter(object):
     dataset's first step, and puts the run's DrivenMesh objects into `driven`."""
 
     def __init__(self, driver: str, cfg, result_root, name: Optional[str] = None):
-        self.cfg, self.image_offset, self.state_offset, self.driven, self.meter = cfg, 0, 0, [], None
+        self.cfg, self.image_offset, self.state_offset, self.driven, self.meter, self.rigid_log = cfg, 0, 0, [], None, None
         self.painter = field_paint.painter_from_cfg(cfg, cfg.get("gaussian"))
         self.paths = output_paths(driver, result_root, name, cfg.video_name, cfg.get("save_particles"), cfg.get("save_gaussians"),
                                   cfg.get("save_mesh"), None if self.painter is None else self.painter.quantity)
@@ -158,8 +160,12 @@ class FrameWriter(object):
             self.meter = contact.ContactMeter(model)
             if not (model.colliders or model.field_colliders):
                 print("report_contacts: sim.colliders is empty, reporting the box walls alone")
-        return dict(export=self.paths["gaussians"] is not None or self.paths["meshes"] is not None, draw_styles=draw_styles,
-                    draw_mesh_styles=mesh_styles, painter=self.painter, meter=self.meter)
+        options = dict(export=self.paths["gaussians"] is not None or self.paths["meshes"] is not None, draw_styles=draw_styles,
+                       draw_mesh_styles=mesh_styles, painter=self.painter, meter=self.meter)
+        if model.rigid_bodies:
+            self.rigid_log = rigid.RigidLog(model)
+            options["rigid_log"] = self.rigid_log
+        return options
 
     def targets(self, step: int, views: Sequence[str]) -> Dict:
         """The files of frame `step`, by the keys of output_paths: a list per view for the images, one path or None otherwise."""
@@ -198,3 +204,8 @@ class FrameWriter(object):
         if self.meter is not None:
             print(f"contacts: {self.meter.write_csv(self.paths['contacts'])}")
             print(self.meter.summary())
+        if self.rigid_log is not None:
+            path = self.paths["contacts"].with_name(f"rigid_{self.cfg.video_name}.csv")      # beside the contacts file
+            print(f"rigid bodies: {self.rigid_log.write_csv(path)}")
+            for line in self.rigid_log.mass_ratio_notes():
+                print(line)

@@ -55,7 +55,7 @@ def denormalize_points(points: torch.Tensor, sections: Sequence[int], state_init
 def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: int, cameras: Sequence, background: torch.Tensor,
                      denormalize: bool = False, on_frame: Optional[Callable[[int, Dict], None]] = None,
                      render: bool = True, export: bool = False, draw_styles=None, draw_mesh_styles=None, painter=None, meter=None,
-                     init_state=None) -> Iterator[Dict]:
+                     init_state=None, rigid_log=None) -> Iterator[Dict]:
     """Generator over frames 0..eval_steps.  Yields {'step', 'x', 'F', 'means3D', 'images': [per camera]}, from frame 1
     'deform_grad', the bound deformation gradients (K,3,3), and with `render` 'shs', the coefficients the frame was rendered with:
     those of an object with `rotate_sh` are rotated once per frame, before the views, by the polar rotations of its bound
@@ -71,7 +71,8 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
     over one shared range, with `render` 'paint_images', the views once more at sh_degree 0 with those coefficients (colliders
     drawn in alike), and with `export` 'paint_gaussians', the frame's Gaussians with the painted DC colour and no rest coefficients.
     With `meter` (contact.ContactMeter of the model) every step's contact rows are recorded before the colliders move, one frame per
-    step; nothing is read back here."""
+    step; nothing is read back here.  With `rigid_log` (rigid.RigidLog of a model with rigid bodies) every step's body states are
+    kept on the device after the bodies moved, with the contact mass each was moved by."""
     device = model.device
     state_initializer = MPMStateInitializer(model)
     statics_initializer = MPMStaticsInitializer(model)
@@ -148,7 +149,9 @@ def simulate_objects(model: MPMModel, objects: List[SceneObject], eval_steps: in
         if meter is not None:
             meter.record()
             meter.frame()
-        model.step_colliders()                                         # moving colliders: one substep further (sim/colliders.py)
+        model.step_colliders()                                         # moving colliders and rigid bodies: one substep further
+        if rigid_log is not None:
+            rigid_log.after_step()
         F = plasticity(F)
         state.from_torch(F=F)
         statics_initializer.update(statics, step)

@@ -24,6 +24,17 @@ come after all analytic entries (list order is the order of application, and fie
 most MAX_FIELD_COLLIDERS of them.  parse_colliders returns them as MeshCollider objects behind the analytic ones; a model builds
 each one's field once (MeshCollider.build -> FieldCollider, which is what nm_mpm_set_field_colliders takes: pack_fields).  A
 FieldCollider can also be made from any signed distance field directly.  pack() stays what it was: analytic colliders only.
+
+Rigid bodies (include/neuma_hip.h "Rigid bodies"; fp64 restatement: neuma_amd/extras/rigid.py): a sphere or box entry may be a body
+that the material and gravity move, on the device, forward only.
+
+        - {type: sphere, center: [0.5, 0.7, 0.5], radius: 0.08, surface: sticky, dynamic: true, density: 4000}
+        - {type: box, center: [0.5, 0.5, 0.5], half: [0.2, 0.02, 0.05], kinematic: true, angular_velocity: [0, 6, 0]}
+
+`dynamic: true` needs `mass` or `density` (simulation units: the unit cube, rho * vol masses - mass = density * volume);
+`kinematic: true` keeps `velocity` and `angular_velocity` whatever pushes it (a paddle; mass defaults to 1 and moves nothing);
+`angular_velocity` is in simulation axes; `gravity: false` switches the model's gravity off for the body.  The entry parses into
+its Sphere / Box with a RigidBody record in `.body`; pack_bodies() makes the array nm_mpm_set_rigid_bodies takes.
 """
 import ctypes as C
 import math
@@ -63,9 +74,53 @@ class _Collider:
         object.__setattr__(self, "friction", float(self.friction))
         object.__setattr__(self, "velocity", _vec3(self.velocity, "velocity"))
 
+    body = None      # Sphere / Box: the RigidBody record of an entry that is a rigid body
+
     @property
     def moving(self) -> bool:
-        return any(a != 0.0 for a in self.velocity)
+        """a prescribed mover, which the host advances (a rigid body is moved on the device instead)"""
+        return self.body is None and any(a != 0.0 for a in self.velocity)
+
+
+@dataclass(frozen=True)
+class RigidBody:
+    """What makes a sphere or box entry a rigid body: mass M, body-frame principal inertia I_b, the initial angular velocity
+    (simulation axes), whether the model's gravity acts on it, and whether it is kinematic (keeps v and w, ignores impulses)."""
+    mass: float = 1.0
+    inertia: Tuple[float, float, float] = (1.0, 1.0, 1.0)
+    angular_velocity: Tuple[float, float, float] = (0.0, 0.0, 0.0)
+    gravity: bool = True
+    kinematic: bool = False
+
+    def __post_init__(self) -> None:
+        if not (float(self.mass) > 0.0 and math.isfinite(float(self.mass))):
+            raise ValueError(f"mass: must be positive (got {self.mass})")
+        object.__setattr__(self, "mass", float(self.mass))
+        inertia = _vec3(self.inertia, "inertia")
+        if not all(a > 0.0 for a in inertia):
+            raise ValueError(f"inertia: must be positive (got {inertia})")
+        object.__setattr__(self, "inertia", inertia)
+        object.__setattr__(self, "angular_velocity", _vec3(self.angular_velocity, "angular_velocity"))
+
+    @property
+    def flags(self) -> int:
+        return (1 if self.kinematic else 0) | (0 if self.gravity else 2)      # NM_RIGID_KINEMATIC | NM_RIGID_NO_GRAVITY
+
+
+def volume(c) -> float:
+    """of a Sphere or Box"""
+    if isinstance(c, Sphere):
+        return 4.0 / 3.0 * math.pi * c.radius ** 3
+    return 8.0 * c.half[0] * c.half[1] * c.half[2]
+
+
+def principal_inertia(c, mass: float) -> Tuple[float, float, float]:
+    """Body-frame principal inertia of a solid Sphere (2/5 M r^2) or Box (M/3 (hy^2 + hz^2, hx^2 + hz^2, hx^2 + hy^2))."""
+    if isinstance(c, Sphere):
+        i = 0.4 * mass * c.radius ** 2
+        return (i, i, i)
+    hx, hy, hz = (a * a for a in c.half)
+    return (mass / 3.0 * (hy + hz), mass / 3.0 * (hx + hz), mass / 3.0 * (hx + hy))
 
 
 @dataclass(frozen=True)
@@ -93,6 +148,7 @@ class Sphere(_Collider):
     shape_code = 1      # NM_COLLIDER_SPHERE
     center: Tuple[float, float, float] = (0.0, 0.0, 0.0)
     radius: float = 0.0
+    body: Optional[RigidBody] = None
 
     def __post_init__(self) -> None:
         self._check_common()
@@ -112,6 +168,7 @@ class Box(_Collider):
     center: Tuple[float, float, float] = (0.0, 0.0, 0.0)
     half: Tuple[float, float, float] = (0.0, 0.0, 0.0)
     rot: Tuple[float, ...] = field(default=_IDENTITY)
+    body: Optional[RigidBody] = None
 
     def __post_init__(self) -> None:
         self._check_common()
@@ -253,6 +310,40 @@ def euler_xyz_deg_to_rot(angles) -> Tuple[float, ...]:
             -sb, cb * sa, cb * ca)
 
 
+_BODY_KEYS = ("mass", "density", "angular_velocity", "gravity")
+
+
+def _rigid_body(node, shape) -> Optional[RigidBody]:
+    """The RigidBody record of one `sim.colliders` entry (None: a static or prescribed collider); shape: its Sphere / Box."""
+    dynamic, kinematic = bool(node.get("dynamic", False)), bool(node.get("kinematic", False))
+    if not (dynamic or kinematic):
+        for key in _BODY_KEYS:
+            if node.get(key) is not None:
+                raise ValueError(f"{key}: only a rigid body takes it (set dynamic: true or kinematic: true)")
+        return None
+    if dynamic and kinematic:
+        raise ValueError("kinematic: give either dynamic or kinematic, not both")
+    which = "dynamic" if dynamic else "kinematic"
+    if not isinstance(shape, (Sphere, Box)):
+        raise ValueError(f"{which}: only a sphere or a box can be a rigid body (got {node.get('type')})")
+    mass, density = node.get("mass"), node.get("density")
+    if mass is not None and density is not None:
+        raise ValueError("density: give either mass or density, not both")
+    if density is not None:
+        if not (float(density) > 0.0 and math.isfinite(float(density))):
+            raise ValueError(f"density: must be positive (got {density})")
+        mass = float(density) * volume(shape)
+    elif mass is None:
+        if dynamic:
+            raise ValueError("mass: a dynamic body needs mass or density")
+        mass = 1.0
+    if not (float(mass) > 0.0 and math.isfinite(float(mass))):
+        raise ValueError(f"mass: must be positive (got {mass})")
+    return RigidBody(mass=float(mass), inertia=principal_inertia(shape, float(mass)),
+                     angular_velocity=node.get("angular_velocity", (0.0, 0.0, 0.0)), gravity=bool(node.get("gravity", True)),
+                     kinematic=kinematic)
+
+
 def parse_collider(node, index: int = 0):
     """One entry of `sim.colliders` (a dict; config nodes are dicts) -> Plane / Sphere / Box / MeshCollider.  Errors name the entry
     and the field."""
@@ -263,16 +354,23 @@ def parse_collider(node, index: int = 0):
                   velocity=node.get("velocity", (0.0, 0.0, 0.0)))
     try:
         if kind == "plane":
-            return Plane(point=node.get("point", (0.0, 0.0, 0.0)), normal=node.get("normal", (0.0, 1.0, 0.0)), **common)
+            shape = Plane(point=node.get("point", (0.0, 0.0, 0.0)), normal=node.get("normal", (0.0, 1.0, 0.0)), **common)
+            _rigid_body(node, shape)
+            return shape
         if kind == "sphere":
-            return Sphere(center=node.get("center", (0.0, 0.0, 0.0)), radius=node.get("radius", 0.0), **common)
+            shape = Sphere(center=node.get("center", (0.0, 0.0, 0.0)), radius=node.get("radius", 0.0), **common)
+            body = _rigid_body(node, shape)
+            return shape if body is None else replace(shape, body=body)
         if kind == "box":
             euler, rot = node.get("euler_xyz_deg"), node.get("rot")
             if euler is not None and rot is not None:
                 raise ValueError("rot: give either euler_xyz_deg or rot, not both")
             rot = euler_xyz_deg_to_rot(euler) if euler is not None else (_IDENTITY if rot is None else rot)
-            return Box(center=node.get("center", (0.0, 0.0, 0.0)), half=node.get("half", (0.0, 0.0, 0.0)), rot=rot, **common)
+            shape = Box(center=node.get("center", (0.0, 0.0, 0.0)), half=node.get("half", (0.0, 0.0, 0.0)), rot=rot, **common)
+            body = _rigid_body(node, shape)
+            return shape if body is None else replace(shape, body=body)
         if kind == "mesh":
+            _rigid_body(node, None)
             return _mesh_collider(node, common)
         raise ValueError(f"shape: unknown shape {kind!r} (one of {sorted(SHAPES) + ['mesh']})")
     except ValueError as e:
@@ -319,6 +417,26 @@ def pack(colliders: Sequence):
         out.radius = c.radius if isinstance(c, Sphere) else 0.0
         out.half = (C.c_float * 3)(*(c.half if isinstance(c, Box) else (0.0, 0.0, 0.0)))
         out.rot = (C.c_float * 9)(*(c.rot if isinstance(c, Box) else _IDENTITY))
+    return arr
+
+
+def bodies_of(colliders: Sequence) -> List[Tuple[int, RigidBody]]:
+    """(index, RigidBody) of the entries of an analytic list that are rigid bodies, in list order"""
+    return [(i, c.body) for i, c in enumerate(colliders) if c.body is not None]
+
+
+def pack_bodies(colliders: Sequence):
+    """ctypes array of nm_rigid_body for nm_mpm_set_rigid_bodies, one per body entry of the analytic list (None without bodies)."""
+    bodies = bodies_of(colliders)
+    if not bodies:
+        return None
+    arr = (L.nm_rigid_body * len(bodies))()
+    for out, (i, b) in zip(arr, bodies):
+        out.collider = i
+        out.flags = b.flags
+        out.mass = b.mass
+        out.inertia = (C.c_double * 3)(*b.inertia)
+        out.angular_velocity = (C.c_double * 3)(*b.angular_velocity)
     return arr
 
 
@@ -369,6 +487,11 @@ def describe(colliders: Sequence, drawn: bool = False) -> str:
             geo = f"box center={c.center} half={c.half} rot={tuple(round(a, 6) for a in c.rot)}"
         surf = c.surface + (f" mu={c.friction}" if c.surface == "friction" else "")
         lines.append(f"  [{i}] {geo} surface={surf} velocity={c.velocity}")
+        if c.body is not None:
+            b = c.body
+            lines.append(f"      rigid body: {'kinematic' if b.kinematic else 'dynamic'} mass={b.mass:.6g} "
+                         f"inertia={tuple(round(a, 9) for a in b.inertia)} angular_velocity={b.angular_velocity} "
+                         f"gravity={'on' if b.gravity else 'off'}")
     return "\n".join(lines)
 
 

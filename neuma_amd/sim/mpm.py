@@ -257,8 +257,45 @@ class MPMModel(Model):
     # -- colliders (no reference counterpart; sim/colliders.py)
     @property
     def colliders(self):
-        """The analytic colliders this model steps against (Plane / Sphere / Box objects, in the order they are applied)."""
+        """The analytic colliders this model steps against (Plane / Sphere / Box objects, in the order they are applied), where
+        they are NOW.  With rigid bodies that is one (bodies, 19) read-back of rigid_state() - a host synchronisation, meant for
+        drawing and file writing: a body's entry comes back at its current centre and orientation, with its current velocity and,
+        in `.body.angular_velocity`, its current angular velocity."""
+        if not self.rigid_bodies or self._handle is None:
+            return list(self._colliders)
+        from ..extras import rigid as _rigid
+        out = list(self._colliders)
+        for (i, body), row in zip(self.rigid_bodies, self.rigid_state().cpu().numpy()):
+            c, _ = _rigid.posed(out[i], _rigid.RigidState.from_row(row))
+            out[i] = replace(c, velocity=tuple(float(a) for a in row[13:16]),
+                             body=replace(body, angular_velocity=tuple(float(a) for a in row[16:19])))
+        return out
+
+    def rigid_rows(self) -> Tensor:
+        """(1 + colliders, 9) fp64 on the model's device: the contact rows the last step_colliders() moved the bodies by (the layout
+        of contact().rows).  Asynchronous; only on a model with rigid bodies, after a step."""
+        rows = torch.empty(1 + len(self._colliders) + len(self._field_colliders), CONTACT_COLS, dtype=torch.float64, device=self.device)
+        L.check(L.lib().nm_mpm_rigid_rows(self.handle(), rows.data_ptr(), self._stream()), "nm_mpm_rigid_rows")
+        return rows
+
+    @property
+    def prescribed_colliders(self):
+        """The analytic colliders as the host holds them: static and prescribed entries where they are now, rigid bodies at the
+        pose they were given (their state lives on the device: rigid_state()).  No read-back."""
         return list(self._colliders)
+
+    @property
+    def rigid_bodies(self):
+        """[(index into `colliders`, RigidBody)] of the entries that are rigid bodies (sim/colliders.py), in list order"""
+        return _colliders.bodies_of(self._colliders)
+
+    def rigid_state(self) -> Tensor:
+        """(bodies, 19) fp64 on the model's device, one row per body in list order: c[3], q[4] (wxyz), P[3], Lc[3], v[3], w[3]
+        (include/neuma_hip.h "Rigid bodies").  Asynchronous: nothing is read back to the host."""
+        out = torch.empty(len(self.rigid_bodies), RIGID_STATE_COLS, dtype=torch.float64, device=self.device)
+        if out.shape[0]:
+            L.check(L.lib().nm_mpm_rigid_state(self.handle(), out.data_ptr(), self._stream()), "nm_mpm_rigid_state")
+        return out
 
     @property
     def field_colliders(self):
@@ -269,7 +306,9 @@ class MPMModel(Model):
     def set_colliders(self, colliders) -> None:
         """Replace the model's colliders (dicts as in the `sim.colliders` config list, or collider objects; [] / None removes
         them).  Host-only: may be called between any two substeps.  Colliders act on MPMModel.forward / backward (the per-operator
-        path); the fused roll-out, forward_extra and sharded models refuse them.  `type: mesh` entries / MeshCollider objects
+        path); the fused roll-out, forward_extra and sharded models refuse them.  Entries with `dynamic: true` / `kinematic: true`
+        (or Sphere / Box objects with a `.body`) become rigid bodies, (re)started from the pose and velocities given here; a model
+        with bodies is forward only.  `type: mesh` entries / MeshCollider objects
         (behind all analytic ones) have their signed distance field built here, once, on the model's device; FieldCollider objects
         are taken as they are (phi is moved to the device if it is elsewhere)."""
         if self.exchange is not None:
@@ -283,26 +322,38 @@ class MPMModel(Model):
                 phi = c.phi if torch.is_tensor(c.phi) else torch.from_numpy(np.array(c.phi))
                 c = replace(c, phi=phi.to(device=self.device, dtype=torch.float32).contiguous())
             built.append(c)
+        had_bodies = bool(self.rigid_bodies)
         self._colliders, self._field_colliders = analytic, built
         if self._handle is not None:      # (a handle created later takes them along: handle())
-            self._upload_colliders()
+            self._upload_colliders(restart_bodies=had_bodies or bool(self.rigid_bodies))
 
-    def _upload_colliders(self) -> None:
+    def _upload_colliders(self, restart_bodies: bool = True) -> None:
+        """restart_bodies: the rigid bodies are (re)created from the host list; False (a prescribed mover advanced): the library
+        keeps them, with their device state, across a list of the same length"""
+        bodies = _colliders.pack_bodies(self._colliders) if restart_bodies else None
+        if restart_bodies and (bodies is not None or L.lib().nm_mpm_num_rigid_bodies(self._handle) != 0):
+            L.check(L.lib().nm_mpm_set_rigid_bodies(self._handle, 0, None), "nm_mpm_set_rigid_bodies")
         arr = _colliders.pack(self._colliders)
         L.check(L.lib().nm_mpm_set_colliders(self._handle, len(self._colliders), arr), "nm_mpm_set_colliders")
         arr = _colliders.pack_fields(self._field_colliders)
         L.check(L.lib().nm_mpm_set_field_colliders(self._handle, len(self._field_colliders), arr), "nm_mpm_set_field_colliders")
+        if bodies is not None:
+            with torch.cuda.device(self.device):
+                L.check(L.lib().nm_mpm_set_rigid_bodies(self._handle, len(bodies), bodies), "nm_mpm_set_rigid_bodies")
 
     def step_colliders(self) -> None:
-        """Advance the centres of the moving colliders - and the lattice origins of the moving field colliders - by velocity * dt
-        (one substep) and re-upload; nothing when none moves."""
+        """One substep further: the rigid bodies take the impulse of the last forward (nm_mpm_rigid_step, on the device, nothing
+        read back - so call contact() before this); then the centres of the prescribed movers - and the lattice origins of the
+        moving field colliders - advance by velocity * dt on the host and are uploaded again.  Nothing when nothing moves."""
+        if self.rigid_bodies and self._handle is not None:
+            L.check(L.lib().nm_mpm_rigid_step(self._handle, self._stream()), "nm_mpm_rigid_step")
         if not any(c.moving for c in self._colliders + self._field_colliders):
             return
         dt = float(self.constant.dt)
         self._colliders = [c.advanced(dt) if c.moving else c for c in self._colliders]
         self._field_colliders = [c.advanced(dt) if c.moving else c for c in self._field_colliders]
         if self._handle is not None:      # (a handle created later takes them along: handle())
-            self._upload_colliders()
+            self._upload_colliders(restart_bodies=False)
 
     def __del__(self):
         try:
@@ -334,6 +385,9 @@ class MPMModel(Model):
 
     def backward(self, statics: MPMStatics, state_curr: MPMState, state_next: MPMState, tape=None) -> None:
         """mpm.py:299-319.  Reads state_next.particle.*_grad, writes state_curr.particle.*_grad."""
+        if self.rigid_bodies:
+            raise NotImplementedError("rigid bodies: forward only (the model holds colliders with `dynamic: true` / `kinematic: true`; "
+                                      "backward differentiates static and prescribed colliders only)")
         pc, pn = state_curr.particle, state_next.particle
         n = pc.x.shape[0]
         dev = pc.x.device
@@ -399,6 +453,7 @@ class MPMModel(Model):
 
 
 CONTACT_COLS = 9      # NM_CONTACT_COLS
+RIGID_STATE_COLS = 19  # NM_RIGID_STATE_COLS
 
 
 @dataclass
